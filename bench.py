@@ -12,6 +12,11 @@ in the global batch (micro-batched through the pipeline stages).
 Prefill is untimed warm-up state; W warm-up decode steps run untimed;
 exactly K steps are timed between barrier+synchronize fences; the
 elapsed time is MAX over ranks.
+
+A plain run does only that.  ``--full`` adds the steady-state TTFT
+measurement (a second, timed prefill); ``--dump-outputs DIR`` writes the
+token ids the last timed step returned, so two builds can be compared
+output for output (ids and weights are seeded, identical run to run).
 """
 
 from __future__ import annotations
@@ -50,7 +55,30 @@ def parse_args():
                    help="disable hipGraph-captured decode (debugging)")
     p.add_argument("--graph", action="store_true",
                    help="force hipGraph decode even at large batch")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not "
+                        "need: steady-state TTFT (a second, timed prefill; "
+                        "reported as config.p50_ttft_ms)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step returned (the next-token ids, one per "
+                        "sequence of the global batch) to DIR/tokens.npy "
+                        "as float32")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, tokens):
+    """Write the last timed step's result as the caller received it: the
+    per-micro-batch token-id tensors, concatenated in batch order."""
+    import os
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = torch.cat([t.reshape(-1) for t in tokens]).cpu()
+    # vocab ids are far below 2**24, so float32 holds them exactly
+    np.save(os.path.join(out_dir, "tokens.npy"),
+            flat.numpy().astype(np.float32))
 
 
 def main():
@@ -123,15 +151,18 @@ def main():
         if use_gpu:
             torch.cuda.synchronize()
 
-    # ---- prefill (untimed state setup; measured separately for TTFT) ----
-    # one throwaway prefill first: hipBLASLt GEMM heuristics/code-objects
-    # warm up on first use of each shape (~1.4 s one-time, not TTFT)
-    worker.prefill(ids, micro, n_micro, args.prefill)
-    sync()
-    t_pf = time.perf_counter()
+    # ---- prefill (untimed state setup) ----
     tokens = worker.prefill(ids, micro, n_micro, args.prefill)
     sync()
-    ttft_s = time.perf_counter() - t_pf
+    ttft_s = None
+    if args.full:
+        # TTFT is measured on a second prefill: the first one is a
+        # throwaway, hipBLASLt GEMM heuristics/code-objects warm up on
+        # first use of each shape (~1.4 s one-time, not TTFT)
+        t_pf = time.perf_counter()
+        tokens = worker.prefill(ids, micro, n_micro, args.prefill)
+        sync()
+        ttft_s = time.perf_counter() - t_pf
 
     if worker.is_first and tokens is None:
         raise RuntimeError("stage 0 did not receive tokens")
@@ -199,9 +230,12 @@ def main():
                 "micro_batches": n_micro,
                 "weights": (f"int{args.bits}-w{args.bits}a16"
                             if args.quant else "bf16"),
-                "p50_ttft_ms": round(ttft_s * 1000, 3),
             },
         }
+        if ttft_s is not None:
+            result["config"]["p50_ttft_ms"] = round(ttft_s * 1000, 3)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, tokens)
         print(json.dumps(result), flush=True)
 
     if world > 1:

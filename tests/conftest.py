@@ -1,5 +1,15 @@
+import sys
+from pathlib import Path
+
 import pytest
 import torch
+
+# the package is built and imported in-tree (no install step): make it
+# importable however pytest was started (`pytest tests` puts tests/, not
+# the repository root, on sys.path)
+_ROOT = str(Path(__file__).resolve().parent.parent)
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
 
 
 def pytest_configure(config):

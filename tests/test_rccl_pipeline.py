@@ -238,8 +238,12 @@ def test_rccl_serve_cli_end_to_end(tiny_checkpoint, tmp_path):
          "--model", str(tiny_checkpoint), "--port", str(port)],
         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
         cwd=str(tmp_path),
+        # hide any GPUs from the ranks: this test is the gloo/CPU stack on
+        # every host (with GPUs visible the ranks would pick nccl and
+        # need one device each)
         env={**os.environ,
-             "PYTHONPATH": str(Path(__file__).parent.parent)})
+             "PYTHONPATH": str(Path(__file__).parent.parent),
+             "HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": ""})
     try:
         deadline = time.time() + 120
         up = False
@@ -266,7 +270,7 @@ def test_rccl_serve_cli_end_to_end(tiny_checkpoint, tmp_path):
         resp = conn.getresponse()
         body = json.loads(resp.read())
         conn.close()
-        assert resp.status == 200
+        assert resp.status == 200, body
         assert body["usage"]["completion_tokens"] >= 1
     finally:
         proc.terminate()
