@@ -171,9 +171,18 @@ def softcap(x, cap: float):
 
 
 _GEMV_MAX_M = 64  # above this, dequant + hipBLASLt GEMM wins
+_LONG_K = 16384   # gemm64 / kseg serve only K at least this long
 
 
 _DQ_CACHE_BYTES = 0
+
+
+def _dq_cache_cap() -> Optional[float]:
+    """dq-cache budget in bytes (MLXS_AMD_DQ_CACHE_GB overrides the
+    96 GB default); None when MLXS_AMD_NO_DQ_CACHE disables caching."""
+    if os.environ.get("MLXS_AMD_NO_DQ_CACHE"):
+        return None
+    return float(os.environ.get("MLXS_AMD_DQ_CACHE_GB", "96")) * (1 << 30)
 
 
 def _dq_cache_ok(nbytes: int) -> bool:
@@ -184,65 +193,73 @@ def _dq_cache_ok(nbytes: int) -> bool:
     MLXS_AMD_NO_DQ_CACHE=1 disables caching entirely;
     MLXS_AMD_DQ_CACHE_GB overrides the budget."""
     global _DQ_CACHE_BYTES
-    if os.environ.get("MLXS_AMD_NO_DQ_CACHE"):
-        return False
-    cap = float(os.environ.get("MLXS_AMD_DQ_CACHE_GB", "96")) * (1 << 30)
-    if _DQ_CACHE_BYTES + nbytes > cap:
+    cap = _dq_cache_cap()
+    if cap is None or _DQ_CACHE_BYTES + nbytes > cap:
         return False
     _DQ_CACHE_BYTES += nbytes
     return True
 
 
-def linear(x, weight, bias=None):
-    """Dense linear.  The MFMA decode GEMV (MLXS_AMD_DENSE_GEMV=1) was
-    a NEGATIVE result at batch-64 decode shapes: hipBLASLt's small-GEMM
-    kernels run ~13 us in-graph and the split-K fp32-atomic traffic
-    (M*O*4*nk bytes) rivals the weight bytes on small-O projections
-    (docs/PERFORMANCE.md).  Kept for shape-specific re-tuning."""
-    if (os.environ.get("MLXS_AMD_DENSE_GEMV")
-            and _use_hip(x) and weight.dtype == torch.bfloat16
-            and x.dtype == torch.bfloat16 and weight.shape[-1] % 32 == 0
-            and weight.is_contiguous()):
-        lead = x.shape[:-1]
-        x2 = x.reshape(-1, x.shape[-1])
-        if 0 < x2.shape[0] <= 64:
-            y = _require_ext("linear").dense_gemv(x2, weight)
-            if bias is not None:
-                y = y + bias
-            return y.reshape(*lead, y.shape[-1])
-    # LDS-tiled M<=64 GEMM (dense_gemm64): measured 1.0-1.5 TB/s vs
-    # hipBLASLt's 3.4-5.5 on the llama-70B shapes after three
-    # iterations (staging flattening, row-tile amortization) — kept as
-    # opt-in infrastructure (MLXS_AMD_GEMM64=1), NOT the default
-    if (os.environ.get("MLXS_AMD_GEMM64")
-            and _use_hip(x) and weight.dtype == torch.bfloat16
-            and x.dtype == torch.bfloat16 and weight.shape[-1] >= 16384
-            and weight.shape[-1] % 8 == 0 and weight.is_contiguous()):
-        lead = x.shape[:-1]
-        x2 = x.reshape(-1, x.shape[-1])
-        if 0 < x2.shape[0] <= 64:
-            y = _require_ext("linear").dense_gemm64(x2, weight)
-            if bias is not None:
-                y = y + bias
-            return y.reshape(*lead, y.shape[-1])
-    # K-segmented coalesced-A GEMM (gemm_kseg.hip) — DEFAULT on exactly
-    # the regime it measured faster than hipBLASLt (3.96 vs 3.27 TB/s,
-    # tools/gemm_kseg_probe.py): M<=64 decode with K-long huge
-    # projections (llama-70B down_proj class).  Everything else stays
-    # on the library.  MLXS_AMD_NO_KSEG=1 opts out.
+def _small_m_route(M: int, O: int, K: int, x_dtype, w_dtype,
+                   w_contiguous: bool, on_gpu: bool):
+    """Which in-house M<=64 dense GEMM serves y[M, O] = x[M, K] @ W[O, K]^T:
+    ``(name, ksegs)`` with name in gemv / gemm64 / kseg (ksegs is None
+    except for kseg), or None for the library (hipBLASLt).  First match
+    wins, in this order:
+
+    gemv (MLXS_AMD_DENSE_GEMV=1) — the LDS-free MFMA decode GEMV, a
+      NEGATIVE result at batch-64 decode shapes: hipBLASLt's small-GEMM
+      kernels run ~13 us in-graph and the split-K fp32-atomic traffic
+      (M*O*4*nk bytes) rivals the weight bytes on small-O projections
+      (docs/PERFORMANCE.md).  Kept for shape-specific re-tuning.
+    gemm64 (MLXS_AMD_GEMM64=1) — the LDS-tiled GEMM: measured 1.0-1.5
+      TB/s vs hipBLASLt's 3.4-5.5 on the llama-70B shapes after three
+      iterations (staging flattening, row-tile amortization); opt-in
+      infrastructure, NOT the default.
+    kseg — the K-segmented coalesced-A GEMM (gemm_kseg.hip), DEFAULT on
+      exactly the regime it measured faster than hipBLASLt (3.96 vs
+      3.27 TB/s, tools/gemm_kseg_probe.py): K-long huge projections
+      (llama-70B down_proj class).  MLXS_AMD_NO_KSEG=1 opts out."""
+    if not (on_gpu and x_dtype == torch.bfloat16
+            and w_dtype == torch.bfloat16 and w_contiguous
+            and 0 < M <= _GEMV_MAX_M):
+        return None
+    if os.environ.get("MLXS_AMD_DENSE_GEMV") and K % 32 == 0:
+        return "gemv", None
+    if os.environ.get("MLXS_AMD_GEMM64") and K >= _LONG_K and K % 8 == 0:
+        return "gemm64", None
     if (not os.environ.get("MLXS_AMD_NO_KSEG")
-            and _use_hip(x) and weight.dtype == torch.bfloat16
-            and x.dtype == torch.bfloat16
-            and weight.shape[-1] >= 16384 and weight.shape[0] >= 8192
-            and weight.shape[-1] % 256 == 0 and weight.is_contiguous()):
-        lead = x.shape[:-1]
-        x2 = x.reshape(-1, x.shape[-1])
-        if 0 < x2.shape[0] <= 64:
-            ksegs = max(1, min(16, 512 // max(1, weight.shape[0] // 64)))
-            y = _require_ext("linear").gemm_m64_kseg(x2, weight, ksegs)
-            if bias is not None:
-                y = y + bias
-            return y.reshape(*lead, y.shape[-1])
+            and K >= _LONG_K and O >= 8192 and K % 256 == 0):
+        return "kseg", max(1, min(16, 512 // max(1, O // 64)))
+    return None
+
+
+def _small_m_linear(x, weight, bias, name: str, ksegs):
+    ext = _require_ext("linear")
+    x2 = x.reshape(-1, x.shape[-1])
+    if name == "gemv":
+        y = ext.dense_gemv(x2, weight)
+    elif name == "gemm64":
+        y = ext.dense_gemm64(x2, weight)
+    else:
+        y = ext.gemm_m64_kseg(x2, weight, ksegs)
+    if bias is not None:
+        y = y + bias
+    return y.reshape(*x.shape[:-1], y.shape[-1])
+
+
+def linear(x, weight, bias=None):
+    """Dense linear: an in-house M<=64 GEMM where _small_m_route picks
+    one, else the library."""
+    K = weight.shape[-1]
+    # this runs per projection per decode step: skip the routing work
+    # for the short-K weights that only the opt-in gemv could take
+    if K >= _LONG_K or os.environ.get("MLXS_AMD_DENSE_GEMV"):
+        route = _small_m_route(x.numel() // max(1, x.shape[-1]),
+                               weight.shape[0], K, x.dtype, weight.dtype,
+                               weight.is_contiguous(), _use_hip(x))
+        if route is not None:
+            return _small_m_linear(x, weight, bias, *route)
     return torch.nn.functional.linear(x, weight, bias)
 
 
@@ -452,9 +469,13 @@ def grouped_expert_mlp_subs(x, gate_w, up_w, down_w, subs, max_tok: int = 4):
 
 
 def _to_f16_cached(x: torch.Tensor) -> torch.Tensor:
-    """bf16 -> fp16 cast (exact), memoized on the tensor object: sibling
+    """bf16 -> fp16 cast, memoized on the tensor object: sibling
     projections sharing one activation (o_proj + shared experts + MoE
-    within a layer) pay the cast launch once.  Activations are fresh
+    within a layer) pay the cast launch once.  The cast is exact only
+    for bf16 values whose magnitude fits fp16's range: it overflows to
+    inf above 65504 and rounds, then flushes to zero, the smallest
+    bf16 values (below fp16's normal range, |v| < 2^-14); there is no
+    clamp.  Activations are fresh
     objects per step (never mutated in place), so the cache cannot go
     stale; under graph capture the cast is captured once and the cached
     buffer is reused by later ops in the same graph."""
@@ -503,7 +524,8 @@ def grouped_expert_mlp_quant_subs(x, gate, up, down, subs,
     """Quantized grouped experts over prebuilt 16-token sub-ranges via
     the fp16-dequant MFMA kernels (moe_w4f16.hip): fused gate+up+SiLU
     in one pass, pk_fma dequant (~16 VALU per 8 weights vs ~36 for the
-    old per-element cvt+fma kernel), activations cast to fp16 (exact)."""
+    old per-element cvt+fma kernel), activations cast to fp16 (exact
+    within fp16's range, unclamped — see _to_f16_cached)."""
     ext = _require_ext("grouped_expert_mlp_quant")
     sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt = subs
     P = sorted_tok.shape[0]
@@ -577,8 +599,8 @@ def expert_dequant_resident(gate, up, down, group_size: int, bits: int):
     pw = 32 // bits
     # dense bytes = packed words * elems/word * 2 B, per matrix
     est = 2 * pw * (gate[0].numel() + up[0].numel() + down[0].numel())
-    cap = float(os.environ.get("MLXS_AMD_DQ_CACHE_GB", "96")) * (1 << 30)
-    if os.environ.get("MLXS_AMD_NO_DQ_CACHE") or _DQ_CACHE_BYTES + est > cap:
+    cap = _dq_cache_cap()
+    if cap is None or _DQ_CACHE_BYTES + est > cap:
         return None
     res = expert_dequant(gate, up, down, group_size, bits)
     return res if getattr(gate[0], "_mlxs_dq", None) is not None else None
@@ -589,14 +611,9 @@ def grouped_expert_mlp_quant(x, gate, up, down, weights, indices,
     """Quantized stacked experts: gate/up/down are (w_q, scales, biases)
     triplets with stacked [E, ...] layout."""
     if _use_hip(x):
-        ext = _require_ext("grouped_expert_mlp_quant")
+        _require_ext("grouped_expert_mlp_quant")
         E = gate[0].shape[0]
-        P = indices.numel()
-        if P >= _MOE_GEMM_MIN_N:
-            H = x.shape[-1]
-            I = down[0].shape[-1] * (32 // bits)
-            pw = 32 // bits
-
+        if indices.numel() >= _MOE_GEMM_MIN_N:
             return _moe_prefill_gemm(
                 x, None, None, None, weights, indices,
                 dequant_all=lambda: expert_dequant(gate, up, down,

@@ -20,9 +20,6 @@
 
 #include "hip_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #define AP_WAVES 4
 #define AP_BLOCK (AP_WAVES * WAVE)
 #define AP_QTILE (AP_WAVES * 16)  // 64 q rows per block
@@ -65,21 +62,21 @@ __global__ __launch_bounds__(AP_BLOCK) void attn_prefill_kernel(
   constexpr int VTS = AP_KTILE + 8;  // transposed-row stride (16B-aligned)
 
   // ---- load Q fragments (A layout): lane: row wq0+(l&15), 16B at kslice ----
-  bf16x8 qfrag[NKS];
+  bf16x8_t qfrag[NKS];
   {
     int row = min(wq0 + (lane & 15), T - 1);  // clamped; masked on write
     const short* qr = qbase + (long)row * Dk + (lane >> 4) * 8;
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks)
-      qfrag[ks] = *reinterpret_cast<const bf16x8*>(qr + ks * 32);
+      qfrag[ks] = *reinterpret_cast<const bf16x8_t*>(qr + ks * 32);
   }
 
   float m_run[4], l_run[4];
-  f32x4 oacc[NDH];
+  float4v oacc[NDH];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { m_run[r] = -1e30f; l_run[r] = 0.0f; }
 #pragma unroll
-  for (int dh = 0; dh < NDH; ++dh) oacc[dh] = f32x4{0, 0, 0, 0};
+  for (int dh = 0; dh < NDH; ++dh) oacc[dh] = float4v{0, 0, 0, 0};
 
   // causal bounds: per-wave compute range, block-uniform loop (the V
   // tile is staged once per block and shared by all four waves)
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(AP_BLOCK) void attn_prefill_kernel(
     __syncthreads();
     if (t0 >= wave_s_hi) continue;  // this wave's rows see no keys here
     // ---- QK^T: two 16-key column halves ----
-    f32x4 c0 = {0, 0, 0, 0}, c1 = {0, 0, 0, 0};
+    float4v c0 = {0, 0, 0, 0}, c1 = {0, 0, 0, 0};
     {
       const int key0 = t0 + (lane & 15);
       const int key1 = t0 + 16 + (lane & 15);
@@ -120,8 +117,8 @@ __global__ __launch_bounds__(AP_BLOCK) void attn_prefill_kernel(
       const short* kr1 = kbase + (long)min(key1, S - 1) * Dk + (lane >> 4) * 8;
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
-        bf16x8 kf0 = *reinterpret_cast<const bf16x8*>(kr0 + ks * 32);
-        bf16x8 kf1 = *reinterpret_cast<const bf16x8*>(kr1 + ks * 32);
+        bf16x8_t kf0 = *reinterpret_cast<const bf16x8_t*>(kr0 + ks * 32);
+        bf16x8_t kf1 = *reinterpret_cast<const bf16x8_t*>(kr1 + ks * 32);
         c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[ks], kf0, c0, 0, 0, 0);
         c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[ks], kf1, c1, 0, 0, 0);
       }
@@ -179,15 +176,15 @@ __global__ __launch_bounds__(AP_BLOCK) void attn_prefill_kernel(
       }
     // (same-wave LDS write->read: hipcc inserts the lgkmcnt wait itself)
     // ---- P @ V ----
-    bf16x8 pfrag = *reinterpret_cast<const bf16x8*>(
+    bf16x8_t pfrag = *reinterpret_cast<const bf16x8_t*>(
         p_lds + (lane & 15) * AP_KTILE + (lane >> 4) * 8);
 #pragma unroll
     for (int dh = 0; dh < NDH; ++dh) {
       // B-frag of V: one contiguous b128 read from the transposed row
-      bf16x8 vf = *reinterpret_cast<const bf16x8*>(
+      bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(
           v_lds + (dh * 16 + (lane & 15)) * VTS + (lane >> 4) * 8);
-      f32x4 prev = oacc[dh];
-      f32x4 scaled;
+      float4v prev = oacc[dh];
+      float4v scaled;
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) scaled[reg] = prev[reg] * alpha[reg];
       oacc[dh] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfrag, vf, scaled, 0, 0, 0);
@@ -269,13 +266,13 @@ __global__ void mfma_probe_kernel(const short* __restrict__ A,  // [16][32]
                                   const short* __restrict__ Bm, // [32][16]
                                   float* __restrict__ D) {      // [16][16]
   const int lane = threadIdx.x & (WAVE - 1);
-  bf16x8 a, b;
+  bf16x8_t a, b;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     a[j] = *reinterpret_cast<const __bf16*>(A + (lane & 15) * 32 + (lane >> 4) * 8 + j);
     b[j] = *reinterpret_cast<const __bf16*>(Bm + ((lane >> 4) * 8 + j) * 16 + (lane & 15));
   }
-  f32x4 c = {0, 0, 0, 0};
+  float4v c = {0, 0, 0, 0};
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 #pragma unroll
   for (int reg = 0; reg < 4; ++reg)

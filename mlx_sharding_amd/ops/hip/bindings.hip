@@ -121,6 +121,18 @@ bool row_view2(const torch::Tensor& t, long& rows, long& rstride) {
   return false;
 }
 
+// Optional fp32 split-K scratch [M, O]: allocated only when the launcher
+// will split (nk > 1); otherwise undefined, and the launcher gets null.
+torch::Tensor splitk_scratch(int nk, int M, int O,
+                             const torch::TensorOptions& opts) {
+  if (nk <= 1) return torch::Tensor();
+  return torch::empty({M, O}, opts.dtype(torch::kFloat32));
+}
+
+float* f32_or_null(const torch::Tensor& t) {
+  return t.defined() ? t.data_ptr<float>() : nullptr;
+}
+
 torch::Tensor rms_norm(torch::Tensor x, torch::Tensor w, double eps,
                        double w_off) {
   check_bf16(x, "x");
@@ -373,7 +385,6 @@ torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor Bm) {
   return D;
 }
 
-// x [M, H] bf16, wq [O, H*bits/32] uint32/int32, scales/biases [O, H/gs]
 // Dense bf16 decode GEMV: y = x @ w^T on MFMA (M <= 64)
 torch::Tensor dense_gemv(torch::Tensor x, torch::Tensor w) {
   check_bf16(x, "x");
@@ -385,14 +396,9 @@ torch::Tensor dense_gemv(torch::Tensor x, torch::Tensor w) {
   TORCH_CHECK(M <= 64 && H % 32 == 0, "dense_gemv needs M<=64, H%32==0");
   auto y = torch::empty({M, O}, xc.options());
   const int nk = bf16_gemv_nsplit(M, O, H);
-  torch::Tensor yf;
-  float* yfp = nullptr;
-  if (nk > 1) {
-    yf = torch::empty({M, O}, xc.options().dtype(torch::kFloat32));
-    yfp = yf.data_ptr<float>();
-  }
-  launch_bf16_gemv_mfma(xc.data_ptr(), w.data_ptr(), y.data_ptr(), yfp, nk,
-                        M, O, H, cur_stream());
+  auto yf = splitk_scratch(nk, M, O, xc.options());
+  launch_bf16_gemv_mfma(xc.data_ptr(), w.data_ptr(), y.data_ptr(),
+                        f32_or_null(yf), nk, M, O, H, cur_stream());
   return y;
 }
 
@@ -449,17 +455,13 @@ torch::Tensor dense_gemm64(torch::Tensor x, torch::Tensor w) {
   TORCH_CHECK(M <= 64 && H % 8 == 0, "dense_gemm64 needs M<=64, H%8==0");
   auto y = torch::empty({M, O}, xc.options());
   const int nk = bf16_gemm_m64_nsplit(M, O, H);
-  torch::Tensor yf;
-  float* yfp = nullptr;
-  if (nk > 1) {
-    yf = torch::empty({M, O}, xc.options().dtype(torch::kFloat32));
-    yfp = yf.data_ptr<float>();
-  }
-  launch_bf16_gemm_m64(xc.data_ptr(), w.data_ptr(), y.data_ptr(), yfp, nk, M,
-                       O, H, cur_stream());
+  auto yf = splitk_scratch(nk, M, O, xc.options());
+  launch_bf16_gemm_m64(xc.data_ptr(), w.data_ptr(), y.data_ptr(),
+                       f32_or_null(yf), nk, M, O, H, cur_stream());
   return y;
 }
 
+// x [M, H] bf16, wq [O, H*bits/32] uint32/int32, scales/biases [O, H/gs]
 torch::Tensor w4a16_gemv(torch::Tensor x, torch::Tensor wq,
                          torch::Tensor scales, torch::Tensor biases,
                          int64_t gs, int64_t bits) {
@@ -470,16 +472,12 @@ torch::Tensor w4a16_gemv(torch::Tensor x, torch::Tensor wq,
   auto y = torch::empty({M, O}, xc.options());
   if (M >= 8 && H % 32 == 0 && gs % 32 == 0) {
     const int nk = w4a16_mfma_nsplit(M, O, H);
-    torch::Tensor yf;
-    float* yfp = nullptr;
-    if (nk > 1) {
-      yf = torch::empty({M, O}, xc.options().dtype(torch::kFloat32));
-      yfp = yf.data_ptr<float>();
-    }
+    auto yf = splitk_scratch(nk, M, O, xc.options());
     launch_w4a16_mfma(xc.data_ptr(), wq.contiguous().data_ptr(),
                       scales.contiguous().data_ptr(),
-                      biases.contiguous().data_ptr(), y.data_ptr(), yfp, nk,
-                      M, O, H, (int)gs, (int)bits, cur_stream());
+                      biases.contiguous().data_ptr(), y.data_ptr(),
+                      f32_or_null(yf), nk, M, O, H, (int)gs, (int)bits,
+                      cur_stream());
   } else {
     launch_w4a16_gemv(xc.data_ptr(), wq.contiguous().data_ptr(),
                       scales.contiguous().data_ptr(),
@@ -634,16 +632,12 @@ torch::Tensor w4f16_gemv(torch::Tensor x, torch::Tensor wq,
   auto y = torch::empty({M, O},
                         xc.options().dtype(torch::kBFloat16));
   const int nk = w4f16_gemv_nsplit(M, O, H);
-  torch::Tensor yf;
-  float* yfp = nullptr;
-  if (nk > 1) {
-    yf = torch::empty({M, O}, xc.options().dtype(torch::kFloat32));
-    yfp = yf.data_ptr<float>();
-  }
+  auto yf = splitk_scratch(nk, M, O, xc.options());
   launch_w4f16_gemv(xc.data_ptr(), wq.contiguous().data_ptr(),
                     scales.contiguous().data_ptr(),
-                    biases.contiguous().data_ptr(), y.data_ptr(), yfp, nk, M,
-                    O, H, (int)gs, (int)bits, cur_stream());
+                    biases.contiguous().data_ptr(), y.data_ptr(),
+                    f32_or_null(yf), nk, M, O, H, (int)gs, (int)bits,
+                    cur_stream());
   return y;
 }
 

@@ -200,9 +200,6 @@ extern "C" void launch_moe_down_grouped(const void* h, const void* down_w,
 #define MF_LDS (MF_CH + 16)  // rows 16B-aligned, 8-bank shift per row
 #define MF_NSL (MF_CH / 32)
 
-typedef __bf16 mfbf16x8 __attribute__((ext_vector_type(8)));
-typedef float mff32x4 __attribute__((ext_vector_type(4)));
-
 // No LDS, no barriers: B-fragments are read straight from the 16 token
 // rows in global (same strided 16-rows-x-16B pattern as the A loads —
 // quarter-wave groups cover a full 64 B line per row).  x is tiny and
@@ -235,20 +232,20 @@ __global__ __launch_bounds__(MF_BLOCK) void moe_gateup_mfma_kernel(
   const int tok_r = sorted_tok[p0 + min(lane & 15, cnt - 1)];
   const short* xrow = x + (long)tok_r * H;
 
-  mff32x4 gacc = {0, 0, 0, 0}, uacc = {0, 0, 0, 0};
+  float4v gacc = {0, 0, 0, 0}, uacc = {0, 0, 0, 0};
   // full MF_NSL-slice batches (all global loads issued before the MFMA
   // block — guide trap 4(b)), then an exact tail loop: without zeroed
   // LDS columns, clamped duplicate loads would double-count.
   const int nsl_total = H / 32;  // binding requires H % 32 == 0
   int sl = 0;
   for (; sl + MF_NSL <= nsl_total; sl += MF_NSL) {
-    mfbf16x8 ga[MF_NSL], ua[MF_NSL], ba[MF_NSL];
+    bf16x8_t ga[MF_NSL], ua[MF_NSL], ba[MF_NSL];
 #pragma unroll
     for (int i = 0; i < MF_NSL; ++i) {
       const int koff = (sl + i) * 32 + (lane >> 4) * 8;
-      ga[i] = *reinterpret_cast<const mfbf16x8*>(grow + koff);
-      ua[i] = *reinterpret_cast<const mfbf16x8*>(urow + koff);
-      ba[i] = *reinterpret_cast<const mfbf16x8*>(xrow + koff);
+      ga[i] = *reinterpret_cast<const bf16x8_t*>(grow + koff);
+      ua[i] = *reinterpret_cast<const bf16x8_t*>(urow + koff);
+      ba[i] = *reinterpret_cast<const bf16x8_t*>(xrow + koff);
     }
 #pragma unroll
     for (int i = 0; i < MF_NSL; ++i) {
@@ -258,9 +255,9 @@ __global__ __launch_bounds__(MF_BLOCK) void moe_gateup_mfma_kernel(
   }
   for (; sl < nsl_total; ++sl) {  // < MF_NSL leftover slices, once
     const int koff = sl * 32 + (lane >> 4) * 8;
-    mfbf16x8 ga = *reinterpret_cast<const mfbf16x8*>(grow + koff);
-    mfbf16x8 ua = *reinterpret_cast<const mfbf16x8*>(urow + koff);
-    mfbf16x8 ba = *reinterpret_cast<const mfbf16x8*>(xrow + koff);
+    bf16x8_t ga = *reinterpret_cast<const bf16x8_t*>(grow + koff);
+    bf16x8_t ua = *reinterpret_cast<const bf16x8_t*>(urow + koff);
+    bf16x8_t ba = *reinterpret_cast<const bf16x8_t*>(xrow + koff);
     gacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga, ba, gacc, 0, 0, 0);
     uacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ua, ba, uacc, 0, 0, 0);
   }
@@ -303,16 +300,16 @@ __global__ __launch_bounds__(MF_BLOCK) void moe_down_mfma_kernel(
   // never written)
   const short* hrow = h + (long)(p0 + min(lane & 15, cnt - 1)) * I;
 
-  mff32x4 acc = {0, 0, 0, 0};
+  float4v acc = {0, 0, 0, 0};
   const int nsl_total = I / 32;  // binding requires I % 32 == 0
   int sl = 0;
   for (; sl + MF_NSL <= nsl_total; sl += MF_NSL) {
-    mfbf16x8 da[MF_NSL], ba[MF_NSL];
+    bf16x8_t da[MF_NSL], ba[MF_NSL];
 #pragma unroll
     for (int i = 0; i < MF_NSL; ++i) {
       const int koff = (sl + i) * 32 + (lane >> 4) * 8;
-      da[i] = *reinterpret_cast<const mfbf16x8*>(drow + koff);
-      ba[i] = *reinterpret_cast<const mfbf16x8*>(hrow + koff);
+      da[i] = *reinterpret_cast<const bf16x8_t*>(drow + koff);
+      ba[i] = *reinterpret_cast<const bf16x8_t*>(hrow + koff);
     }
 #pragma unroll
     for (int i = 0; i < MF_NSL; ++i)
@@ -320,8 +317,8 @@ __global__ __launch_bounds__(MF_BLOCK) void moe_down_mfma_kernel(
   }
   for (; sl < nsl_total; ++sl) {
     const int koff = sl * 32 + (lane >> 4) * 8;
-    mfbf16x8 da = *reinterpret_cast<const mfbf16x8*>(drow + koff);
-    mfbf16x8 ba = *reinterpret_cast<const mfbf16x8*>(hrow + koff);
+    bf16x8_t da = *reinterpret_cast<const bf16x8_t*>(drow + koff);
+    bf16x8_t ba = *reinterpret_cast<const bf16x8_t*>(hrow + koff);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, ba, acc, 0, 0, 0);
   }
 
@@ -580,9 +577,6 @@ extern "C" void launch_moe_gate_subranges(
 // kernel paid ~38 VALU per word PER TOKEN).
 // ---------------------------------------------------------------------------
 
-typedef __bf16 mw4bf16x8 __attribute__((ext_vector_type(8)));
-typedef float mw4f32x4 __attribute__((ext_vector_type(4)));
-
 #define MW_WAVES 4
 #define MW_BLOCK (MW_WAVES * WAVE)
 #define MW_MTOK 32
@@ -618,8 +612,8 @@ __global__ __launch_bounds__(MW_BLOCK) void moe_w4_mfma_kernel(
   // back-to-back MFMAs on one accumulator serialize on the dependent-
   // accumulator latency; parity-split chains double the dependency
   // distance.  Summed in the epilogue.
-  mw4f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
-  mw4f32x4 acc0b = {0, 0, 0, 0}, acc1b = {0, 0, 0, 0};
+  float4v acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+  float4v acc0b = {0, 0, 0, 0}, acc1b = {0, 0, 0, 0};
   const int wrow_r = min(row0 + (lane & 15), O - 1);
   const long ebase = (long)e * O;
   const unsigned int* wrow = wq + (ebase + wrow_r) * words_per_row;
@@ -635,7 +629,7 @@ __global__ __launch_bounds__(MW_BLOCK) void moe_w4_mfma_kernel(
     unsigned int wbuf[MW_NSL * (BITS == 4 ? 1 : 2)];
     short sraw[MW_NSL], braw[MW_NSL];  // raw bf16: converting at
                                        // load-site forces a vmcnt wait
-    mw4bf16x8 b0v[MW_NSL], b1v[MW_NSL];
+    bf16x8_t b0v[MW_NSL], b1v[MW_NSL];
 #pragma unroll
     for (int i = 0; i < MW_NSL; ++i) {
       const int kk = (sl + i) * 32 + (lane >> 4) * 8;
@@ -647,12 +641,12 @@ __global__ __launch_bounds__(MW_BLOCK) void moe_w4_mfma_kernel(
       }
       sraw[i] = srow[kk / gs];
       braw[i] = brow[kk / gs];
-      b0v[i] = *reinterpret_cast<const mw4bf16x8*>(xr0 + kk);
-      b1v[i] = *reinterpret_cast<const mw4bf16x8*>(xr1 + kk);
+      b0v[i] = *reinterpret_cast<const bf16x8_t*>(xr0 + kk);
+      b1v[i] = *reinterpret_cast<const bf16x8_t*>(xr1 + kk);
     }
     // dequant the WHOLE batch into registers first: a VALU-built A
     // fragment feeding its MFMA directly is a RAW issue-stall
-    mw4bf16x8 afv[MW_NSL];
+    bf16x8_t afv[MW_NSL];
 #pragma unroll
     for (int i = 0; i < MW_NSL; ++i) {
       const float sg = bfbits2f(sraw[i]);
@@ -686,7 +680,7 @@ __global__ __launch_bounds__(MW_BLOCK) void moe_w4_mfma_kernel(
     const int kk = sl * 32 + (lane >> 4) * 8;
     const float sg = bfbits2f(srow[kk / gs]);
     const float bg = bfbits2f(brow[kk / gs]);
-    mw4bf16x8 af;
+    bf16x8_t af;
     if (BITS == 4) {
       const unsigned int bits = wrow[kk / 8];
 #pragma unroll
@@ -701,8 +695,8 @@ __global__ __launch_bounds__(MW_BLOCK) void moe_w4_mfma_kernel(
         af[4 + j] = (__bf16)(sg * (float)((b1 >> (8 * j)) & MASK) + bg);
       }
     }
-    mw4bf16x8 b0f = *reinterpret_cast<const mw4bf16x8*>(xr0 + kk);
-    mw4bf16x8 b1f = *reinterpret_cast<const mw4bf16x8*>(xr1 + kk);
+    bf16x8_t b0f = *reinterpret_cast<const bf16x8_t*>(xr0 + kk);
+    bf16x8_t b1f = *reinterpret_cast<const bf16x8_t*>(xr1 + kk);
     acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b0f, acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b1f, acc1, 0, 0, 0);
   }

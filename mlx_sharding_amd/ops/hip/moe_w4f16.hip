@@ -23,7 +23,8 @@
 //
 // Net: ~16 VALU per 8 weights (shift + and_or + pk_add + pk_fma on
 // pairs), scale/bias splats hoisted per quant group.  Activations
-// arrive as fp16 (exact bf16->fp16 cast done by the caller); gate+up
+// arrive as fp16 (bf16->fp16 cast done by the caller, exact within
+// fp16's range — see ops._to_f16_cached); gate+up
 // (+SiLU) are fused in one kernel like the bf16 MFMA pair, removing
 // the separate up pass and the glu launch.
 //
@@ -32,56 +33,12 @@
 // deepseek_v2.py:101-112 + nn.quantize, shard/utils.py:54-65).
 
 #include "hip_common.h"
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float wf32x4 __attribute__((ext_vector_type(4)));
+#include "splitk.h"
+#include "w4f16_dequant.h"
 
 #define WF_WAVES 4
 #define WF_BLOCK (WF_WAVES * WAVE)
 #define WF_NSL 8
-
-union f16pack {
-  unsigned int u;
-  f16x2 h;
-};
-
-// dequant one repacked u32 (8 x 4-bit) into 4 fp16 pairs
-template <int BITS>
-__device__ __forceinline__ void dq8(unsigned int w, f16x2 s2, f16x2 b2,
-                                    f16x8* out) {
-  f16x2* op = reinterpret_cast<f16x2*>(out);
-  if (BITS == 4) {
-    const f16x2 c = {(_Float16)(-1032.0f), (_Float16)(-1032.0f)};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f16pack p;
-      p.u = ((w >> (4 * j)) & 0x000F000Fu) | 0x64006400u;  // v_and_or_b32
-      f16x2 v = p.h + c;          // exact small int q-8
-      op[j] = v * s2 + b2;        // v_pk_fma_f16
-    }
-  }
-}
-
-// w8: two repacked u32s -> 4 fp16 pairs
-__device__ __forceinline__ void dq8_w8(unsigned int w0, unsigned int w1,
-                                       f16x2 s2, f16x2 b2, f16x8* out) {
-  const f16x2 c = {(_Float16)(-1152.0f), (_Float16)(-1152.0f)};
-  f16x2* op = reinterpret_cast<f16x2*>(out);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    f16pack p;
-    p.u = ((w0 >> (8 * j)) & 0x00FF00FFu) | 0x64006400u;
-    op[j] = (p.h + c) * s2 + b2;
-    p.u = ((w1 >> (8 * j)) & 0x00FF00FFu) | 0x64006400u;
-    op[2 + j] = (p.h + c) * s2 + b2;
-  }
-}
-
-__device__ __forceinline__ f16x2 splat2(float v) {
-  const _Float16 h = (_Float16)v;
-  return (f16x2){h, h};
-}
 
 // Batched-loop k-remap: a WF_NSL(=8)-slice batch covers 256 k
 // elements.  Instead of the natural mapping (slice i, quarter-group q
@@ -122,7 +79,6 @@ struct LaneSB {
 // k-offset of slice i for quarter-group q under the batch remap.
 // ONLY valid for 8-slice batches: the q*64 + i*8 tiling covers exactly
 // [0, 256) once; other WF_NSL values would overlap/miss k ranges.
-static_assert(true, "");
 __device__ __forceinline__ int batch_kk(int sl, int q, int i) {
   return sl * 32 + q * 64 + i * 8;
 }
@@ -172,8 +128,8 @@ __global__ __launch_bounds__(WF_BLOCK) void moe_w4f16_gateup_kernel(
   // serialize on the dependent-accumulator latency (the PMC's 54%
   // issue-stall); alternating slices across two chains doubles the
   // dependency distance (summed in the epilogue)
-  wf32x4 gacc = {0, 0, 0, 0}, uacc = {0, 0, 0, 0};
-  wf32x4 gacc2 = {0, 0, 0, 0}, uacc2 = {0, 0, 0, 0};
+  float4v gacc = {0, 0, 0, 0}, uacc = {0, 0, 0, 0};
+  float4v gacc2 = {0, 0, 0, 0}, uacc2 = {0, 0, 0, 0};
   constexpr float QOFF = BITS == 4 ? 8.0f : 128.0f;
   constexpr int WPS = BITS == 4 ? 1 : 2;  // packed words per 8-elem slice
 
@@ -292,7 +248,7 @@ __global__ __launch_bounds__(WF_BLOCK) void moe_w4f16_down_kernel(
   const short* dbr = dbi + (ebase + wr) * ngr;
   const _Float16* hrow = hh + (long)(p0 + min(lane & 15, cnt - 1)) * I;
 
-  wf32x4 acc = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};  // parity-split chains
+  float4v acc = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};  // parity-split chains
   constexpr float QOFF = BITS == 4 ? 8.0f : 128.0f;
   constexpr int WPS = BITS == 4 ? 1 : 2;
 
@@ -389,12 +345,6 @@ struct LaneSBD {
   }
 };
 
-__global__ void w4f16_f32_to_bf16_kernel(const float* __restrict__ src,
-                                         short* __restrict__ dst, long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = (short)__bfloat16_as_ushort(f2bf(src[i]));
-}
-
 template <int MZ, int BITS, int GS>
 __global__ __launch_bounds__(WF_BLOCK) void w4f16_gemv_kernel(
     const _Float16* __restrict__ x,       // [M, H] fp16
@@ -418,9 +368,9 @@ __global__ __launch_bounds__(WF_BLOCK) void w4f16_gemv_kernel(
   for (int z = 0; z < MZ; ++z)
     xrow[z] = x + (long)min(z * 16 + (lane & 15), M - 1) * H;
 
-  wf32x4 acc[MZ];
+  float4v acc[MZ];
 #pragma unroll
-  for (int z = 0; z < MZ; ++z) acc[z] = wf32x4{0, 0, 0, 0};
+  for (int z = 0; z < MZ; ++z) acc[z] = float4v{0, 0, 0, 0};
   constexpr float QOFF = BITS == 4 ? 8.0f : 128.0f;
   constexpr int WPS = BITS == 4 ? 1 : 2;
 
@@ -481,20 +431,9 @@ __global__ __launch_bounds__(WF_BLOCK) void w4f16_gemv_kernel(
   }
 
 #pragma unroll
-  for (int z = 0; z < MZ; ++z) {
-    const int t = z * 16 + (lane & 15);
-    if (t >= M) continue;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int o = row0 + (lane >> 4) * 4 + reg;
-      if (o < O) {
-        if (yf != nullptr)
-          atomicAdd(yf + (long)t * O + o, acc[z][reg]);
-        else
-          y[(long)t * O + o] = (short)__bfloat16_as_ushort(f2bf(acc[z][reg]));
-      }
-    }
-  }
+  for (int z = 0; z < MZ; ++z)
+    store_c_tile_lane(y, yf, acc[z], z * 16 + (lane & 15), M,
+                      row0 + (lane >> 4) * 4, O);
 }
 
 extern "C" int w4f16_gemv_nsplit(int M, int O, int H) {
@@ -536,8 +475,7 @@ extern "C" void launch_w4f16_gemv(const void* x, const void* wq,
                                   const void* sc, const void* bi, void* y,
                                   float* yf, int nk, int M, int O, int H,
                                   int gs, int bits, hipStream_t stream) {
-  if (nk > 1)
-    (void)hipMemsetAsync(yf, 0, (size_t)M * O * sizeof(float), stream);
+  if (nk > 1) launch_f32_zero(yf, (long)M * O, stream);
 #define GV_GS(BB)                                                           \
   do {                                                                      \
     if (gs == 32)                                                           \
@@ -550,11 +488,7 @@ extern "C" void launch_w4f16_gemv(const void* x, const void* wq,
   if (bits == 4) GV_GS(4);
   else GV_GS(8);
 #undef GV_GS
-  if (nk > 1) {
-    const long n = (long)M * O;
-    w4f16_f32_to_bf16_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256),
-                               0, stream>>>(yf, (short*)y, n);
-  }
+  if (nk > 1) launch_f32_to_bf16(yf, y, (long)M * O, stream);
 }
 
 template <int BITS>

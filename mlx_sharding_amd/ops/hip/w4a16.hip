@@ -17,6 +17,7 @@
 // routes through hipBLASLt and these kernels serve memory-tight mode.
 
 #include "hip_common.h"
+#include "splitk.h"
 
 #define QK_BLOCK 256
 #define QK_WAVES (QK_BLOCK / WAVE)
@@ -219,9 +220,6 @@ extern "C" void launch_dequant(const void* wq, const void* scales,
 // partial-sum rounding.
 // ---------------------------------------------------------------------------
 
-typedef __bf16 w4bf16x8 __attribute__((ext_vector_type(8)));
-typedef float w4f32x4 __attribute__((ext_vector_type(4)));
-
 #define QM_WAVES 4
 #define QM_BLOCK (QM_WAVES * WAVE)
 #define QM_MTOK 32
@@ -263,11 +261,11 @@ __global__ __launch_bounds__(QM_BLOCK) void w4a16_mfma_kernel(
   // strips amortize the staging traffic and LDS reads.
   const int row0 = (blockIdx.x * QM_WAVES + wid) * 16 * QM_RT;
 
-  w4f32x4 acc0[QM_RT], acc1[QM_RT];
+  float4v acc0[QM_RT], acc1[QM_RT];
 #pragma unroll
   for (int r = 0; r < QM_RT; ++r) {
-    acc0[r] = w4f32x4{0, 0, 0, 0};
-    acc1[r] = w4f32x4{0, 0, 0, 0};
+    acc0[r] = float4v{0, 0, 0, 0};
+    acc1[r] = float4v{0, 0, 0, 0};
   }
   const unsigned int* wrow[QM_RT];
   const short* srow[QM_RT];
@@ -337,12 +335,12 @@ __global__ __launch_bounds__(QM_BLOCK) void w4a16_mfma_kernel(
       // B fragments: x^T halves (tokens 0-15, 16-31) — shared by all
       // QM_RT row tiles
       const short* xb = x_lds + k0 + (lane >> 4) * 8;
-      w4bf16x8 bf0 = *reinterpret_cast<const w4bf16x8*>(xb + (lane & 15) * QM_LDS);
-      w4bf16x8 bf1 =
-          *reinterpret_cast<const w4bf16x8*>(xb + ((lane & 15) + 16) * QM_LDS);
+      bf16x8_t bf0 = *reinterpret_cast<const bf16x8_t*>(xb + (lane & 15) * QM_LDS);
+      bf16x8_t bf1 =
+          *reinterpret_cast<const bf16x8_t*>(xb + ((lane & 15) + 16) * QM_LDS);
 #pragma unroll
       for (int r = 0; r < QM_RT; ++r) {
-        w4bf16x8 af;
+        bf16x8_t af;
         const float sg = bfbits2f(sraw[r][i]);
         const float bg = bfbits2f(braw[r][i]);
         if (BITS == 4) {
@@ -367,27 +365,13 @@ __global__ __launch_bounds__(QM_BLOCK) void w4a16_mfma_kernel(
 
   // epilogue: D[row=W-row, col=token]; lane writes 4 rows x 1 token per half
   if (row0 >= O) return;
+  const int t = m0 + (lane & 15);  // t < M also bounds the token tile
 #pragma unroll
-  for (int r = 0; r < QM_RT; ++r)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int o = row0 + r * 16 + (lane >> 4) * 4 + reg;
-      if (o < O) {
-        const int t0 = lane & 15;
-        if (yf != nullptr) {  // split-K: fp32 atomic partials
-          if (t0 < mt) atomicAdd(yf + (long)(m0 + t0) * O + o, acc0[r][reg]);
-          if (t0 + 16 < mt)
-            atomicAdd(yf + (long)(m0 + t0 + 16) * O + o, acc1[r][reg]);
-        } else {
-          if (t0 < mt)
-            y[(long)(m0 + t0) * O + o] =
-                (short)__bfloat16_as_ushort(f2bf(acc0[r][reg]));
-          if (t0 + 16 < mt)
-            y[(long)(m0 + t0 + 16) * O + o] =
-                (short)__bfloat16_as_ushort(f2bf(acc1[r][reg]));
-        }
-      }
-    }
+  for (int r = 0; r < QM_RT; ++r) {
+    const int o0 = row0 + r * 16 + (lane >> 4) * 4;
+    store_c_tile_lane(y, yf, acc0[r], t, M, o0, O);
+    store_c_tile_lane(y, yf, acc1[r], t + 16, M, o0, O);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -399,11 +383,6 @@ __global__ __launch_bounds__(QM_BLOCK) void w4a16_mfma_kernel(
 // rows), same split-K-over-grid.y + fp32-atomic machinery as the w4
 // MFMA kernel for small-O shapes.  MZ = 16-token groups (template).
 // ---------------------------------------------------------------------------
-
-typedef __bf16 dgbf16x8 __attribute__((ext_vector_type(8)));
-
-__global__ void f32_to_bf16_kernel(const float* __restrict__ src,
-                                   short* __restrict__ dst, long n);
 
 #define DG_WAVES 4
 #define DG_BLOCK (DG_WAVES * WAVE)
@@ -427,9 +406,9 @@ __global__ __launch_bounds__(DG_BLOCK) void bf16_gemv_mfma_kernel(
   for (int z = 0; z < MZ; ++z)
     xrow[z] = x + (long)min(z * 16 + (lane & 15), M - 1) * H;
 
-  w4f32x4 acc[MZ];
+  float4v acc[MZ];
 #pragma unroll
-  for (int z = 0; z < MZ; ++z) acc[z] = w4f32x4{0, 0, 0, 0};
+  for (int z = 0; z < MZ; ++z) acc[z] = float4v{0, 0, 0, 0};
 
   // k-slices of this split (H % 32 == 0 enforced by the binding)
   const int nsl_total = H / 32;
@@ -439,14 +418,14 @@ __global__ __launch_bounds__(DG_BLOCK) void bf16_gemv_mfma_kernel(
 
   int sl = sl_lo;
   for (; sl + DG_NSL <= sl_hi; sl += DG_NSL) {
-    dgbf16x8 af[DG_NSL], bf[MZ][DG_NSL];
+    bf16x8_t af[DG_NSL], bf[MZ][DG_NSL];
 #pragma unroll
     for (int i = 0; i < DG_NSL; ++i) {
       const int koff = (sl + i) * 32 + (lane >> 4) * 8;
-      af[i] = *reinterpret_cast<const dgbf16x8*>(wrow + koff);
+      af[i] = *reinterpret_cast<const bf16x8_t*>(wrow + koff);
 #pragma unroll
       for (int z = 0; z < MZ; ++z)
-        bf[z][i] = *reinterpret_cast<const dgbf16x8*>(xrow[z] + koff);
+        bf[z][i] = *reinterpret_cast<const bf16x8_t*>(xrow[z] + koff);
     }
 #pragma unroll
     for (int i = 0; i < DG_NSL; ++i)
@@ -457,29 +436,18 @@ __global__ __launch_bounds__(DG_BLOCK) void bf16_gemv_mfma_kernel(
   }
   for (; sl < sl_hi; ++sl) {  // tail slices, once
     const int koff = sl * 32 + (lane >> 4) * 8;
-    dgbf16x8 af = *reinterpret_cast<const dgbf16x8*>(wrow + koff);
+    bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(wrow + koff);
 #pragma unroll
     for (int z = 0; z < MZ; ++z) {
-      dgbf16x8 bf = *reinterpret_cast<const dgbf16x8*>(xrow[z] + koff);
+      bf16x8_t bf = *reinterpret_cast<const bf16x8_t*>(xrow[z] + koff);
       acc[z] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[z], 0, 0, 0);
     }
   }
 
 #pragma unroll
-  for (int z = 0; z < MZ; ++z) {
-    const int t = z * 16 + (lane & 15);
-    if (t >= M) continue;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int o = row0 + (lane >> 4) * 4 + reg;
-      if (o < O) {
-        if (yf != nullptr)
-          atomicAdd(yf + (long)t * O + o, acc[z][reg]);
-        else
-          y[(long)t * O + o] = (short)__bfloat16_as_ushort(f2bf(acc[z][reg]));
-      }
-    }
-  }
+  for (int z = 0; z < MZ; ++z)
+    store_c_tile_lane(y, yf, acc[z], z * 16 + (lane & 15), M,
+                      row0 + (lane >> 4) * 4, O);
 }
 
 extern "C" void launch_bf16_gemv_mfma(const void* x, const void* w, void* y,
@@ -488,9 +456,7 @@ extern "C" void launch_bf16_gemv_mfma(const void* x, const void* w, void* y,
   const int gx = (O + DG_WAVES * 16 - 1) / (DG_WAVES * 16);
   const int mz = (M + 15) / 16;
   dim3 grid((unsigned)gx, (unsigned)nk);
-  if (nk > 1) {
-    (void)hipMemsetAsync(yf, 0, (size_t)M * O * sizeof(float), stream);
-  }
+  if (nk > 1) launch_f32_zero(yf, (long)M * O, stream);
   float* yfp = nk > 1 ? yf : nullptr;
 #define DG_CASE(Z)                                                           \
   case Z:                                                                    \
@@ -506,11 +472,7 @@ extern "C" void launch_bf16_gemv_mfma(const void* x, const void* w, void* y,
       break;
   }
 #undef DG_CASE
-  if (nk > 1) {
-    const long n = (long)M * O;
-    f32_to_bf16_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                         stream>>>(yf, (short*)y, n);
-  }
+  if (nk > 1) launch_f32_to_bf16(yf, y, (long)M * O, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -558,11 +520,11 @@ __global__ __launch_bounds__(DM_BLOCK) void bf16_gemm_m64_kernel(
   const int c_lo = blockIdx.y * ncpb * DM_CH;
   const int c_hi = min(H, c_lo + ncpb * DM_CH);
 
-  w4f32x4 acc[R][4];
+  float4v acc[R][4];
 #pragma unroll
   for (int r = 0; r < R; ++r)
 #pragma unroll
-    for (int z = 0; z < 4; ++z) acc[r][z] = w4f32x4{0, 0, 0, 0};
+    for (int z = 0; z < 4; ++z) acc[r][z] = float4v{0, 0, 0, 0};
 
   const int kk_max = H - 8;
   for (int c0 = c_lo; c0 < c_hi; c0 += DM_CH) {
@@ -589,18 +551,18 @@ __global__ __launch_bounds__(DM_BLOCK) void bf16_gemm_m64_kernel(
       if (row0[r] >= O) continue;  // guard, not break: keep the unroll
       // batch this row-tile's A loads (clamped tail addresses read
       // garbage that multiplies zeroed x columns)
-      dgbf16x8 af[NSL];
+      bf16x8_t af[NSL];
 #pragma unroll
       for (int i = 0; i < NSL; ++i) {
         const int kk = min(c0 + i * 32 + (lane >> 4) * 8, kk_max);
-        af[i] = *reinterpret_cast<const dgbf16x8*>(wrow[r] + kk);
+        af[i] = *reinterpret_cast<const bf16x8_t*>(wrow[r] + kk);
       }
 #pragma unroll
       for (int i = 0; i < NSL; ++i) {
         const short* xb = x_lds + i * 32 + (lane >> 4) * 8;
 #pragma unroll
         for (int z = 0; z < 4; ++z) {
-          dgbf16x8 bf = *reinterpret_cast<const dgbf16x8*>(
+          bf16x8_t bf = *reinterpret_cast<const bf16x8_t*>(
               xb + (z * 16 + (lane & 15)) * DM_LDS);
           acc[r][z] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf,
                                                               acc[r][z],
@@ -614,21 +576,9 @@ __global__ __launch_bounds__(DM_BLOCK) void bf16_gemm_m64_kernel(
   for (int r = 0; r < R; ++r) {
     if (row0[r] >= O) continue;
 #pragma unroll
-    for (int z = 0; z < 4; ++z) {
-      const int t = z * 16 + (lane & 15);
-      if (t >= M) continue;
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int o = row0[r] + (lane >> 4) * 4 + reg;
-        if (o < O) {
-          if (yf != nullptr)
-            atomicAdd(yf + (long)t * O + o, acc[r][z][reg]);
-          else
-            y[(long)t * O + o] =
-                (short)__bfloat16_as_ushort(f2bf(acc[r][z][reg]));
-        }
-      }
-    }
+    for (int z = 0; z < 4; ++z)
+      store_c_tile_lane(y, yf, acc[r][z], z * 16 + (lane & 15), M,
+                        row0[r] + (lane >> 4) * 4, O);
   }
 }
 
@@ -648,17 +598,12 @@ extern "C" void launch_bf16_gemm_m64(const void* x, const void* w, void* y,
                                      hipStream_t stream) {
   const int gx = (O + DM_WAVES * 16 * DM_R - 1) / (DM_WAVES * 16 * DM_R);
   const size_t smem = (size_t)64 * DM_LDS * sizeof(short);
-  if (nk > 1)
-    (void)hipMemsetAsync(yf, 0, (size_t)M * O * sizeof(float), stream);
+  if (nk > 1) launch_f32_zero(yf, (long)M * O, stream);
   float* yfp = nk > 1 ? yf : nullptr;
   bf16_gemm_m64_kernel<DM_R><<<dim3((unsigned)gx, (unsigned)nk),
                                dim3(DM_BLOCK), smem, stream>>>(
       (const short*)x, (const short*)w, (short*)y, yfp, M, O, H);
-  if (nk > 1) {
-    const long n = (long)M * O;
-    f32_to_bf16_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                         stream>>>(yf, (short*)y, n);
-  }
+  if (nk > 1) launch_f32_to_bf16(yf, y, (long)M * O, stream);
 }
 
 extern "C" int bf16_gemv_nsplit(int M, int O, int H) {
@@ -669,12 +614,6 @@ extern "C" int bf16_gemv_nsplit(int M, int O, int H) {
   if (nk > max_nk) nk = max_nk;
   if (nk < 1) nk = 1;
   return nk;
-}
-
-__global__ void f32_to_bf16_kernel(const float* __restrict__ src,
-                                   short* __restrict__ dst, long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = (short)__bfloat16_as_ushort(f2bf(src[i]));
 }
 
 extern "C" int w4a16_mfma_nsplit(int M, int O, int H) {
@@ -697,8 +636,7 @@ extern "C" void launch_w4a16_mfma(const void* x, const void* wq,
   const int mz = (M + QM_MTOK - 1) / QM_MTOK;
   const size_t smem = QM_MTOK * QM_LDS * sizeof(short);
   dim3 grid((unsigned)gx, (unsigned)nk, (unsigned)mz);
-  if (nk > 1)
-    (void)hipMemsetAsync(yf, 0, (size_t)M * O * sizeof(float), stream);
+  if (nk > 1) launch_f32_zero(yf, (long)M * O, stream);
   float* yfp = nk > 1 ? yf : nullptr;
   if (bits == 4)
     w4a16_mfma_kernel<4><<<grid, dim3(QM_BLOCK), smem, stream>>>(
@@ -708,9 +646,5 @@ extern "C" void launch_w4a16_mfma(const void* x, const void* wq,
     w4a16_mfma_kernel<8><<<grid, dim3(QM_BLOCK), smem, stream>>>(
         (const short*)x, (const unsigned int*)wq, (const short*)scales,
         (const short*)biases, (short*)y, yfp, M, O, H, gs);
-  if (nk > 1) {
-    const long n = (long)M * O;
-    f32_to_bf16_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                         stream>>>(yf, (short*)y, n);
-  }
+  if (nk > 1) launch_f32_to_bf16(yf, y, (long)M * O, stream);
 }

@@ -704,6 +704,55 @@ def test_gemm_kseg_under_graph_capture():
     assert rel < 2e-2
 
 
+def _splitk_case(name):
+    """(call, atol) for one split-K launcher at its smallest nk > 1
+    shape; atol is the kernel's own unit-test tolerance."""
+    from mlx_sharding_amd import ops as O_
+    e = ext()
+    torch.manual_seed(3)
+    if name == "dense_gemv":  # nk = 4
+        x = torch.randn(8, 512, dtype=torch.bfloat16, device="cuda") * 0.3
+        w = torch.randn(64, 512, dtype=torch.bfloat16, device="cuda") * 0.3
+        return (lambda: e.dense_gemv(x, w)), 5e-2
+    H = 512 if name == "w4f16_gemv" else 1024
+    scale = 0.05 if name == "w4f16_gemv" else 0.1
+    w = torch.randn(64, H, dtype=torch.bfloat16) * scale
+    wq, sc, bi = (t.cuda() for t in ref.quantize(w, 64, 4))
+    x = torch.randn(8, H, dtype=torch.bfloat16, device="cuda")
+    if name == "w4f16_gemv":  # nk = 4
+        x16, rp = x.to(torch.float16), O_.repack_w4(wq, 4)
+        return (lambda: e.w4f16_gemv(x16, rp, sc, bi, 64, 4)), None
+    # M >= 8: MFMA path, nk = 2
+    return (lambda: e.w4a16_gemv(x, wq, sc, bi, 64, 4)), 6e-2
+
+
+@pytest.mark.parametrize("name", ["w4f16_gemv", "w4a16_gemv", "dense_gemv"])
+def test_splitk_launchers_under_graph_capture(name):
+    """Split-K launchers (zero + atomic partials + convert) must capture
+    and replay correctly in a hipGraph: a zeroing step that is not
+    recorded would make every replay accumulate into stale partials
+    (doubling the output)."""
+    call, atol = _splitk_case(name)
+    eager = call().float()
+    if atol is None:  # test_w4f16_gemv scales its atol by the output
+        atol = 3e-2 * max(1.0, eager.abs().max().item())
+
+    g = torch.cuda.CUDAGraph()
+    out = None
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):  # warmup allocs outside capture
+            out = call()
+    torch.cuda.current_stream().wait_stream(s)
+    with torch.cuda.graph(g):
+        out = call()
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    _close(out, eager, atol=atol)
+
+
 @pytest.mark.gpu
 def test_gemm_m64_kseg_w4_matches_reference():
     """Packed-weight kseg GEMM vs dequant+torch fp32 (infrastructure

@@ -206,6 +206,45 @@ def test_dq_cache_budget(monkeypatch):
     assert not O._dq_cache_ok(1)
 
 
+_ROUTE_ENVS = ("MLXS_AMD_DENSE_GEMV", "MLXS_AMD_GEMM64", "MLXS_AMD_NO_KSEG")
+
+
+def test_linear_routing_table(monkeypatch):
+    """ops.linear's M<=64 kernel choice: precedence gemv > gemm64 > kseg,
+    each behind its env switch and shape/dtype/device guards; everything
+    else goes to the library (None)."""
+    from mlx_sharding_amd import ops as O
+    bf, hf = torch.bfloat16, torch.float16
+    # (env, M, (O, K), x_dtype, w_contiguous, on_gpu, expected)
+    table = [
+        (None, 64, (8192, 16384), bf, True, True, ("kseg", 4)),
+        (None, 64, (8192, 28672), bf, True, True, ("kseg", 4)),
+        (None, 64, (32768, 16384), bf, True, True, ("kseg", 1)),
+        (None, 64, (4096, 16384), bf, True, True, None),
+        (None, 64, (8192, 16512), bf, True, True, None),
+        (None, 65, (8192, 16384), bf, True, True, None),
+        (None, 0, (8192, 16384), bf, True, True, None),
+        (None, 64, (8192, 16384), bf, False, True, None),
+        (None, 64, (8192, 16384), hf, True, True, None),
+        (None, 64, (8192, 16384), bf, True, False, None),
+        ("MLXS_AMD_NO_KSEG", 64, (8192, 16384), bf, True, True, None),
+        ("MLXS_AMD_DENSE_GEMV", 3, (128, 256), bf, True, True,
+         ("gemv", None)),
+        ("MLXS_AMD_DENSE_GEMV", 64, (8192, 16384), bf, True, True,
+         ("gemv", None)),
+        ("MLXS_AMD_GEMM64", 64, (8192, 16384), bf, True, True,
+         ("gemm64", None)),
+        ("MLXS_AMD_GEMM64", 64, (8192, 8192), bf, True, True, None),
+    ]
+    for env, M, (Ow, K), xdt, contig, gpu, want in table:
+        for name in _ROUTE_ENVS:
+            monkeypatch.delenv(name, raising=False)
+        if env is not None:
+            monkeypatch.setenv(env, "1")
+        got = O._small_m_route(M, Ow, K, xdt, bf, contig, gpu)
+        assert got == want, (env, M, Ow, K, xdt, contig, gpu, got)
+
+
 def test_streaming_detokenizer_holds_partial_utf8():
     """Deltas for multi-byte characters are held until complete
     (reference relies on mlx_lm's streaming detokenizer for this)."""
