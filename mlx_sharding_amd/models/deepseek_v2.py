@@ -353,10 +353,22 @@ class DeepseekV2MoE(nn.Module):
         else:
             self.shared_experts = None
 
+    def _gate_groups(self) -> Tuple[int, int]:
+        """(n_group, topk_group) as the gate applies them: plain greedy
+        ignores the config's group fields."""
+        if self.topk_method == "group_limited_greedy":
+            return self.n_group, self.topk_group
+        return 1, 1
+
     def _fused_gate_ok(self, n_tokens: int) -> bool:
-        return (self.topk_method != "group_limited_greedy"
-                and n_tokens <= 128 and self.n_experts <= 64
-                and self.top_k <= 8)
+        # the limits of ops.moe_gate_subranges; anything else takes the
+        # torch gate
+        E, K = self.n_experts, self.top_k
+        n_group, topk_group = self._gate_groups()
+        return (n_tokens <= 128 and 1 <= E <= 256 and 1 <= K <= 8
+                and 1 <= n_group <= 32 and E % n_group == 0
+                and 1 <= topk_group <= n_group
+                and topk_group * (E // n_group) >= K)
 
     def forward(self, x):
         B, T, H = x.shape
@@ -370,9 +382,12 @@ class DeepseekV2MoE(nn.Module):
             # MFMA kernels over resident copies, and the fp16-dequant
             # packed kernels (moe_w4f16.hip) in memory-tight mode
             mt = 16
+            n_group, topk_group = self._gate_groups()
             subs = ops.moe_gate_subranges(logits, self.top_k,
                                           self.routed_scaling_factor,
-                                          self.norm_topk_prob, max_tok=mt)
+                                          self.norm_topk_prob, max_tok=mt,
+                                          n_group=n_group,
+                                          topk_group=topk_group)
             y = self.switch_mlp.forward_subs(flat, subs, mt)
         else:
             logits = self.gate(flat.to(self.gate.weight.dtype)).float()

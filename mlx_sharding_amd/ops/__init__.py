@@ -441,15 +441,21 @@ def _moe_prefill_gemm(x, gate_w, up_w, down_w, weights, indices,
 
 def moe_gate_subranges(router_logits_bf16, top_k: int,
                        routed_scaling_factor: float = 1.0,
-                       norm_topk_prob: bool = False, max_tok: int = 4):
-    """Fused gating: softmax + greedy top-k + expert sort + sub-range
-    build in ONE kernel (N<=128 tokens, E<=64 experts, k<=8)."""
+                       norm_topk_prob: bool = False, max_tok: int = 4,
+                       n_group: int = 1, topk_group: int = 1):
+    """Fused gating: softmax + (group-limited) greedy top-k + expert sort
+    + sub-range build in ONE kernel, with reference.moe_gate semantics.
+
+    Limits (the binding raises outside them): N<=128 tokens, E<=256
+    experts, k<=8, 1<=n_group<=32 with E % n_group == 0,
+    1<=topk_group<=n_group and topk_group*(E/n_group) >= k.
+    n_group=1 is plain greedy."""
     ext = _require_ext("moe_gate_subranges")
     N, E = router_logits_bf16.shape
     s_upper = E + (N * top_k) // max_tok
     return tuple(ext.moe_gate_subranges(router_logits_bf16, top_k, s_upper,
                                         max_tok, routed_scaling_factor,
-                                        norm_topk_prob))
+                                        norm_topk_prob, n_group, topk_group))
 
 
 def grouped_expert_mlp_subs(x, gate_w, up_w, down_w, subs, max_tok: int = 4):

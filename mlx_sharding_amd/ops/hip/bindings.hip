@@ -69,7 +69,7 @@ void launch_moe_w4_mfma(const void*, const void*, const void*, const void*,
                         void*, const int*, const int*, const int*,
                         const int*, int, int, int, int, int, hipStream_t);
 void launch_moe_gate_subranges(const void*, int*, float*, int*, int*, int*,
-                               int, int, int, int, int, float, int,
+                               int, int, int, int, int, float, int, int, int,
                                hipStream_t);
 void launch_moe_w4f16_gateup(const void*, const void*, const void*,
                              const void*, const void*, const void*,
@@ -644,12 +644,27 @@ torch::Tensor w4f16_gemv(torch::Tensor x, torch::Tensor wq,
 std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
                                               int64_t s_upper, int64_t max_tok,
                                               double routed_scaling,
-                                              bool norm_topk) {
+                                              bool norm_topk, int64_t n_group,
+                                              int64_t topk_group) {
   check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [N, E]");
   auto lc = logits.contiguous();
-  const int N = lc.size(0), E = lc.size(1);
-  TORCH_CHECK(N <= 128 && E <= 64 && K <= 8,
-              "fused gate limits: N<=128, E<=64, K<=8");
+  const int64_t N = lc.size(0), E = lc.size(1);
+  // the kernel's LDS arrays are sized for exactly these limits
+  TORCH_CHECK(N <= 128 && E >= 1 && E <= 256 && K >= 1 && K <= 8,
+              "fused gate limits: N<=128, 1<=E<=256, 1<=K<=8 (got N=", N,
+              ", E=", E, ", K=", K, ")");
+  TORCH_CHECK(n_group >= 1 && n_group <= 32 && E % n_group == 0,
+              "fused gate limits: 1<=n_group<=32 and E % n_group == 0 (got E=",
+              E, ", n_group=", n_group, ")");
+  TORCH_CHECK(topk_group >= 1 && topk_group <= n_group,
+              "fused gate limits: 1<=topk_group<=n_group (got topk_group=",
+              topk_group, ", n_group=", n_group, ")");
+  TORCH_CHECK(topk_group * (E / n_group) >= K,
+              "fused gate limits: topk_group*(E/n_group) >= K (got ",
+              topk_group, "*", E / n_group, " < ", K, ")");
+  TORCH_CHECK(max_tok >= 1 && s_upper >= E + (N * K) / max_tok,
+              "fused gate needs max_tok>=1 and s_upper >= E + N*K/max_tok");
   const long P = (long)N * K;
   auto opts = torch::TensorOptions().dtype(torch::kInt32).device(lc.device());
   auto sorted_tok = torch::empty({P}, opts);
@@ -660,9 +675,10 @@ std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
   launch_moe_gate_subranges(lc.data_ptr(), sorted_tok.data_ptr<int>(),
                             sorted_wt.data_ptr<float>(),
                             sub_expert.data_ptr<int>(), sub_off.data_ptr<int>(),
-                            sub_cnt.data_ptr<int>(), N, E, (int)K,
+                            sub_cnt.data_ptr<int>(), (int)N, (int)E, (int)K,
                             (int)s_upper, (int)max_tok, (float)routed_scaling,
-                            norm_topk ? 1 : 0, cur_stream());
+                            norm_topk ? 1 : 0, (int)n_group, (int)topk_group,
+                            cur_stream());
   return {sub_expert, sub_off, sub_cnt, sorted_tok, sorted_wt};
 }
 
@@ -706,7 +722,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_w4_mfma", &moe_w4_mfma);
   m.def("moe_w4f16_gateup", &moe_w4f16_gateup);
   m.def("moe_w4f16_down", &moe_w4f16_down);
-  m.def("moe_gate_subranges", &moe_gate_subranges);
+  m.def("moe_gate_subranges", &moe_gate_subranges, pybind11::arg("logits"),
+        pybind11::arg("top_k"), pybind11::arg("s_upper"),
+        pybind11::arg("max_tok"), pybind11::arg("routed_scaling"),
+        pybind11::arg("norm_topk"), pybind11::arg("n_group") = 1,
+        pybind11::arg("topk_group") = 1);
   m.def("moe_scatter_rows",
         [](torch::Tensor src, torch::Tensor dst, torch::Tensor src_idx,
            torch::Tensor dst_idx) {

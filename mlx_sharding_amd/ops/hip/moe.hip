@@ -431,92 +431,76 @@ extern "C" void launch_moe_gather_reduce(const void* d, const int* pos,
 //
 // Replaces ~20 small torch launches per MoE layer (softmax, topk,
 // argsort/radix-sort, bincount, cumsums, scatter/cummax) with ONE
-// kernel.  Greedy softmax top-k (DeepSeek-V2-Lite's topk_method);
-// group-limited gating falls back to the torch path from Python.
+// kernel.  Softmax top-k, plain greedy (DeepSeek-V2-Lite) or
+// group-limited greedy (DeepSeek-V2: keep the topk_group groups with the
+// largest member probability, pick the top-k among their experts; the
+// weights stay the full-softmax probabilities).
 //
-// Single workgroup; one wave per token batch-slice; E <= 64 experts map
-// one-per-lane.  N <= 64 tokens, top_k <= 8.
+// Single workgroup; one wave per token; lane l holds experts l, 64+l,
+// 128+l, 192+l in registers.  Limits (checked by the binding, the LDS
+// arrays are fixed-size): N <= 128 tokens, E <= 256 experts, top_k <= 8,
+// n_group <= 32 with E % n_group == 0, topk_group * (E / n_group) >= top_k.
 // ---------------------------------------------------------------------------
 
 #define GK_MAXK 8
 #define GK_MAXN 128  // max tokens (LDS arrays below)
+#define GK_MAXE 256  // max experts (LDS arrays below)
+#define GK_WAVES 16
 
-// 1024 threads (16 waves): the top-k argmax is a serial chain of
-// dependent ds_bpermute shuffles per token — more waves = fewer tokens
-// serialized per wave.
-__global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
-    const short* __restrict__ logits,  // [N, E] bf16
-    int* __restrict__ sorted_tok,      // [P]
-    float* __restrict__ sorted_wt,     // [P]
-    int* __restrict__ sub_expert,      // [s_upper]
-    int* __restrict__ sub_off,         // [s_upper]
-    int* __restrict__ sub_cnt,         // [s_upper]
-    int N, int E, int K, int s_upper, int max_tok, float routed_scaling,
-    int norm_topk) {
+// Wave argmax of (v, idx) pairs, ties to the lowest idx; every lane ends
+// up with the winner.
+__device__ __forceinline__ void gk_wave_argmax(float& best, int& bidx) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    float ov = __shfl_xor(best, off, WAVE);
+    int oi = __shfl_xor(bidx, off, WAVE);
+    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+  }
+}
+
+// out[e] = sum_{j<e} ceil(cnt[j] / div) for e in [0, E], by ONE wave:
+// lane l owns experts 4l..4l+3 (E <= 256), then a 6-step wave scan.
+__device__ __forceinline__ void gk_wave_prefix(const int* cnt, int* out, int E,
+                                               int div, int lane) {
+  int c[4];
+  int s = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int e = lane * 4 + j;
+    c[j] = (e < E) ? (cnt[e] + div - 1) / div : 0;
+    s += c[j];
+  }
+  int inc = s;
+#pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    const int o = __shfl_up(inc, off, WAVE);
+    if (lane >= off) inc += o;
+  }
+  int acc = inc - s;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int e = lane * 4 + j;
+    if (e < E) out[e] = acc;
+    acc += c[j];
+  }
+  if (lane == WAVE - 1) out[E] = inc;
+}
+
+// Back half shared by every instantiation: counting-sort the chosen
+// (token, k) pairs by expert and emit the <= max_tok sub-range slots.
+// Needs >= 2 waves; all threads of the block must call it.
+__device__ __forceinline__ void gk_sort_and_subranges(
+    const int* counts, int* starts, int* fill, int* sub_base, const int* tok_e,
+    const float* tok_w, int* __restrict__ sorted_tok,
+    float* __restrict__ sorted_wt, int* __restrict__ sub_expert,
+    int* __restrict__ sub_off, int* __restrict__ sub_cnt, int N, int E, int K,
+    int s_upper, int max_tok, float routed_scaling) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
-  const int nw = blockDim.x / WAVE;
 
-  __shared__ int counts[64];        // per-expert pair count
-  __shared__ int starts[64 + 1];    // exclusive prefix
-  __shared__ int fill[64];          // scatter cursor per expert
-  __shared__ int tok_e[GK_MAXN * GK_MAXK];    // chosen expert per (token, k)
-  __shared__ float tok_w[GK_MAXN * GK_MAXK];  // chosen weight per (token, k)
-
-  for (int i = threadIdx.x; i < 64; i += blockDim.x) {
-    counts[i] = 0;
-    fill[i] = 0;
-  }
-  __syncthreads();
-
-  // ---- per-token softmax + greedy top-k (one wave per token) ----
-  for (int t = wid; t < N; t += nw) {
-    float sc = (lane < E) ? bfbits2f(logits[(long)t * E + lane]) : -1e30f;
-    float mx = wave_max(sc);
-    float p = (lane < E) ? __expf(sc - mx) : 0.0f;
-    float denom = wave_sum(p);
-    p /= denom;
-    float psel = p;
-    float wsum = 0.0f;
-#pragma unroll
-    for (int k = 0; k < GK_MAXK; ++k) {
-      if (k >= K) break;
-      // wave argmax over psel
-      float best = psel;
-      int bidx = lane;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        float ov = __shfl_xor(best, off, WAVE);
-        int oi = __shfl_xor(bidx, off, WAVE);
-        if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
-      }
-      if (lane == 0) {
-        tok_e[t * GK_MAXK + k] = bidx;
-        tok_w[t * GK_MAXK + k] = best;
-        atomicAdd(&counts[bidx], 1);
-      }
-      wsum += best;
-      if (lane == bidx) psel = -1.0f;
-    }
-    if (norm_topk && lane == 0) {
-#pragma unroll
-      for (int k = 0; k < GK_MAXK; ++k) {
-        if (k >= K) break;
-        tok_w[t * GK_MAXK + k] /= (wsum + 1e-20f);
-      }
-    }
-  }
-  __syncthreads();
-
-  // ---- prefix sums (single wave) ----
-  if (threadIdx.x == 0) {
-    int acc = 0;
-    for (int e = 0; e < E; ++e) {
-      starts[e] = acc;
-      acc += counts[e];
-    }
-    starts[E] = acc;
-  }
+  // ---- prefix sums: pair offsets (wave 0), sub-range slots (wave 1) ----
+  if (wid == 0) gk_wave_prefix(counts, starts, E, 1, lane);
+  if (wid == 1) gk_wave_prefix(counts, sub_base, E, max_tok, lane);
   __syncthreads();
 
   // ---- scatter pairs into expert-sorted order ----
@@ -530,17 +514,7 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
 
   // ---- sub-range arrays ----
   // slot layout: expert e's ceil(counts[e]/max_tok) sub-ranges are
-  // contiguous; one thread walks experts to assign slots (E <= 64, cheap)
-  __shared__ int sub_base[64 + 1];
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int e = 0; e < E; ++e) {
-      sub_base[e] = s;
-      s += (counts[e] + max_tok - 1) / max_tok;
-    }
-    sub_base[E] = s;
-  }
-  __syncthreads();
+  // contiguous, experts in order; slots past the live ones are zeroed
   const int S = sub_base[E];
   for (int i = threadIdx.x; i < s_upper; i += blockDim.x) {
     if (i >= S) {
@@ -560,13 +534,164 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
   }
 }
 
+// 1024 threads (16 waves): the top-k argmax is a serial chain of
+// dependent ds_bpermute shuffles per token — more waves = fewer tokens
+// serialized per wave.  R = ceil(E / 64) probabilities per lane.
+template <int R>
+__global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
+    const short* __restrict__ logits,  // [N, E] bf16
+    int* __restrict__ sorted_tok,      // [P]
+    float* __restrict__ sorted_wt,     // [P]
+    int* __restrict__ sub_expert,      // [s_upper]
+    int* __restrict__ sub_off,         // [s_upper]
+    int* __restrict__ sub_cnt,         // [s_upper]
+    int N, int E, int K, int s_upper, int max_tok, float routed_scaling,
+    int norm_topk, int n_group, int topk_group) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+
+  __shared__ int counts[GK_MAXE];        // per-expert pair count
+  __shared__ int starts[GK_MAXE + 1];    // exclusive prefix
+  __shared__ int fill[GK_MAXE];          // scatter cursor per expert
+  __shared__ int sub_base[GK_MAXE + 1];  // first sub-range slot per expert
+  __shared__ int tok_e[GK_MAXN * GK_MAXK];    // chosen expert per (token, k)
+  __shared__ float tok_w[GK_MAXN * GK_MAXK];  // chosen weight per (token, k)
+  __shared__ float probs[GK_WAVES][R * WAVE];  // per-wave row (group scan)
+
+  for (int i = threadIdx.x; i < GK_MAXE; i += blockDim.x) {
+    counts[i] = 0;
+    fill[i] = 0;
+  }
+  __syncthreads();
+
+  const int gsz = E / n_group;  // experts per group
+  int grp[R];                   // group of this lane's r-th expert
+#pragma unroll
+  for (int r = 0; r < R; ++r) grp[r] = min(r * WAVE + lane, E - 1) / gsz;
+
+  // ---- per-token softmax + (group-limited) greedy top-k, one wave per
+  // token; the trip count is block-uniform so the group step may barrier
+  for (int t0 = 0; t0 < N; t0 += GK_WAVES) {
+    const int t = t0 + wid;
+    const bool live = t < N;
+    float p[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) p[r] = 0.0f;
+    if (live) {
+      float sc[R];
+      float mx = -1e30f;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int e = r * WAVE + lane;
+        sc[r] = (e < E) ? bfbits2f(logits[(long)t * E + e]) : -1e30f;
+        mx = fmaxf(mx, sc[r]);
+      }
+      mx = wave_max(mx);
+      float psum = 0.0f;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        p[r] = (r * WAVE + lane < E) ? __expf(sc[r] - mx) : 0.0f;
+        psum += p[r];
+      }
+      const float denom = wave_sum(psum);
+#pragma unroll
+      for (int r = 0; r < R; ++r) p[r] /= denom;
+    }
+
+    // ---- group step: bitmask of the topk_group best groups ----
+    unsigned gmask = 0xffffffffu;
+    if (n_group > 1) {
+      if (live) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (r * WAVE + lane < E) probs[wid][r * WAVE + lane] = p[r];
+      }
+      __syncthreads();
+      if (live) {
+        // lane g scans group g for its max probability; -1 marks lanes
+        // without a group and groups already kept
+        float gs = -1.0f;
+        if (lane < n_group) {
+          const float* row = &probs[wid][lane * gsz];
+          gs = row[0];
+          for (int j = 1; j < gsz; ++j) gs = fmaxf(gs, row[j]);
+        }
+        gmask = 0u;
+        for (int g = 0; g < topk_group; ++g) {
+          float best = gs;
+          int bidx = lane;
+          gk_wave_argmax(best, bidx);
+          gmask |= 1u << bidx;
+          if (lane == bidx) gs = -1.0f;
+        }
+      }
+      __syncthreads();  // row is rewritten by the next token
+    }
+
+    if (live) {
+      // masked, padded and already-picked experts sit at -1, below any
+      // probability (an unmasked probability that underflowed to 0 wins)
+      float psel[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        psel[r] = (r * WAVE + lane < E && ((gmask >> grp[r]) & 1u)) ? p[r]
+                                                                    : -1.0f;
+      float wsum = 0.0f;
+#pragma unroll
+      for (int k = 0; k < GK_MAXK; ++k) {
+        if (k >= K) break;
+        // lane-local argmax over the R registers, then wave argmax
+        float best = psel[0];
+        int bidx = lane;
+#pragma unroll
+        for (int r = 1; r < R; ++r)
+          if (psel[r] > best) { best = psel[r]; bidx = r * WAVE + lane; }
+        gk_wave_argmax(best, bidx);
+        if (lane == 0) {
+          tok_e[t * GK_MAXK + k] = bidx;
+          tok_w[t * GK_MAXK + k] = best;
+          atomicAdd(&counts[bidx], 1);
+        }
+        wsum += best;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (bidx == r * WAVE + lane) psel[r] = -1.0f;
+      }
+      if (norm_topk && lane == 0) {
+#pragma unroll
+        for (int k = 0; k < GK_MAXK; ++k) {
+          if (k >= K) break;
+          tok_w[t * GK_MAXK + k] /= (wsum + 1e-20f);
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  gk_sort_and_subranges(counts, starts, fill, sub_base, tok_e, tok_w,
+                        sorted_tok, sorted_wt, sub_expert, sub_off, sub_cnt, N,
+                        E, K, s_upper, max_tok, routed_scaling);
+}
+
 extern "C" void launch_moe_gate_subranges(
     const void* logits, int* sorted_tok, float* sorted_wt, int* sub_expert,
     int* sub_off, int* sub_cnt, int N, int E, int K, int s_upper, int max_tok,
-    float routed_scaling, int norm_topk, hipStream_t stream) {
-  moe_gate_subranges_kernel<<<dim3(1), dim3(1024), 0, stream>>>(
-      (const short*)logits, sorted_tok, sorted_wt, sub_expert, sub_off,
-      sub_cnt, N, E, K, s_upper, max_tok, routed_scaling, norm_topk);
+    float routed_scaling, int norm_topk, int n_group, int topk_group,
+    hipStream_t stream) {
+  // limits are checked by the caller (bindings.hip::moe_gate_subranges)
+#define GK_LAUNCH(R)                                                         \
+  moe_gate_subranges_kernel<R>                                               \
+      <<<dim3(1), dim3(GK_WAVES * WAVE), 0, stream>>>(                       \
+          (const short*)logits, sorted_tok, sorted_wt, sub_expert, sub_off,  \
+          sub_cnt, N, E, K, s_upper, max_tok, routed_scaling, norm_topk,     \
+          n_group, topk_group)
+  switch ((E + WAVE - 1) / WAVE) {
+    case 1: GK_LAUNCH(1); break;
+    case 2: GK_LAUNCH(2); break;
+    case 3: GK_LAUNCH(3); break;
+    default: GK_LAUNCH(4); break;
+  }
+#undef GK_LAUNCH
 }
 
 // ---------------------------------------------------------------------------

@@ -38,6 +38,38 @@ PRESETS = {
                          "beta_slow": 1, "mscale": 0.707, "mscale_all_dim": 0.707,
                          "original_max_position_embeddings": 4096},
     },
+    # DeepSeek-V2 (236B total, 21B active): group-limited greedy routing
+    # over 160 experts.  Shapes only; far too large to instantiate in tests.
+    "deepseek-v2": {
+        "model_type": "deepseek_v2",
+        "hidden_size": 5120,
+        "num_hidden_layers": 60,
+        "intermediate_size": 12288,
+        "moe_intermediate_size": 1536,
+        "num_attention_heads": 128,
+        "vocab_size": 102400,
+        "rms_norm_eps": 1e-6,
+        "rope_theta": 10000.0,
+        "q_lora_rank": 1536,
+        "kv_lora_rank": 512,
+        "qk_nope_head_dim": 128,
+        "qk_rope_head_dim": 64,
+        "v_head_dim": 128,
+        "n_routed_experts": 160,
+        "n_shared_experts": 2,
+        "num_experts_per_tok": 6,
+        "n_group": 8,
+        "topk_group": 3,
+        "topk_method": "group_limited_greedy",
+        "norm_topk_prob": False,
+        "routed_scaling_factor": 16.0,
+        "first_k_dense_replace": 1,
+        "moe_layer_freq": 1,
+        "max_position_embeddings": 163840,
+        "rope_scaling": {"type": "yarn", "factor": 40.0, "beta_fast": 32,
+                         "beta_slow": 1, "mscale": 1.0, "mscale_all_dim": 1.0,
+                         "original_max_position_embeddings": 4096},
+    },
     "llama-3-8b": {
         "model_type": "llama",
         "hidden_size": 4096,
@@ -144,6 +176,19 @@ PRESETS = {
                          "original_max_position_embeddings": 4096},
     },
 }
+
+# debug-deepseek with DeepSeek-V2's group-limited routing: 96 experts in
+# 8 groups of 12 (more than one 64-lane register row in the fused gate)
+PRESETS["debug-deepseek-grouped"] = dict(
+    PRESETS["debug-deepseek"],
+    n_routed_experts=96,
+    num_experts_per_tok=4,
+    topk_method="group_limited_greedy",
+    n_group=8,
+    topk_group=3,
+    routed_scaling_factor=16.0,
+    norm_topk_prob=False,
+)
 
 
 def get_preset(name: str, quant: bool = False,

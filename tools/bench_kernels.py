@@ -29,9 +29,34 @@ def timeit(fn, iters=50, warmup=10):
     return start.elapsed_time(end) / iters * 1000  # us
 
 
+def bench_grouped_gate(ops, ref, iters, dev="cuda"):
+    """Fused group-limited gating at DeepSeek-V2's routing shape vs the
+    torch sequence it replaces (ref.moe_gate + make_expert_subranges),
+    same process, same timer."""
+    N, E, K, n_group, topk_group = 64, 160, 6, 8, 3
+    g = torch.Generator().manual_seed(1)
+    logits = torch.randn(N, E, generator=g).to(torch.bfloat16).to(dev)
+
+    def fused():
+        return ops.moe_gate_subranges(logits, K, 16.0, False, max_tok=16,
+                                      n_group=n_group, topk_group=topk_group)
+
+    def torch_path():
+        w, idx = ref.moe_gate(logits, K, n_group, topk_group, 16.0, False)
+        return ops.make_expert_subranges(idx, w, E, max_tok=16)
+
+    t_fused = timeit(fused, iters)
+    t_torch = timeit(torch_path, iters)
+    print(f"moe_gate_subranges E=160 grouped  fused {t_fused:8.1f} us   "
+          f"torch gate+subranges {t_torch:8.1f} us   "
+          f"({t_torch / t_fused:.1f}x)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--gate-only", action="store_true",
+                    help="only the grouped-gating fused-vs-torch line")
     args = ap.parse_args()
     from mlx_sharding_amd import ops
     from mlx_sharding_amd.ops import reference as ref
@@ -39,6 +64,10 @@ def main():
     assert ext is not None
     dev = "cuda"
     torch.manual_seed(0)
+
+    if args.gate_only:
+        bench_grouped_gate(ops, ref, args.iters, dev)
+        return
 
     E, H, I, N, K = 64, 2048, 1408, 64, 6
     x = torch.randn(N, H, dtype=torch.bfloat16, device=dev)
@@ -80,6 +109,7 @@ def main():
 
     t = timeit(lambda: ops.moe_gate_subranges(logits, K), args.iters)
     print(f"moe_gate_subranges      {t:8.1f} us")
+    bench_grouped_gate(ops, ref, args.iters, dev)
 
     # w4 variants
     wq = torch.randint(0, 2**31 - 1, (E, I, H // 8), device=dev, dtype=torch.int32)
