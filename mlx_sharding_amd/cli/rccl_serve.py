@@ -20,7 +20,14 @@ def main(argv=None):
                    help="quantize a dense checkpoint to w4a16/w8a16 at load "
                         "(the fast path on MI355X)")
     p.add_argument("--quantize-group-size", type=int, default=64)
+    from ..parallel.batching import MAX_BATCH_LIMIT, env_max_batch
+    p.add_argument("--max-batch", type=int, default=env_max_batch(),
+                   help="continuous batching: decode up to N concurrent "
+                        "requests in one batched step (default "
+                        "MLXS_MAX_BATCH or 1 = off; world size 1 only)")
     args = p.parse_args(argv)
+    if not 1 <= args.max_batch <= MAX_BATCH_LIMIT:
+        p.error(f"--max-batch must be in [1, {MAX_BATCH_LIMIT}]")
 
     from transformers import AutoTokenizer
 
@@ -31,6 +38,9 @@ def main(argv=None):
     from ..utils.loading import load_model
 
     rank, world, device = init_distributed()
+    if args.max_batch > 1 and world > 1:
+        raise SystemExit("--max-batch > 1 batches on one single-stage "
+                         "model; launch rccl-serve with one rank")
     cfg = ModelConfig.load(args.model)
     s, e = split_layers(cfg.num_hidden_layers, world)[rank]
     q = (args.quantize, args.quantize_group_size) if args.quantize else None

@@ -120,12 +120,16 @@ class StageModel(nn.Module):
 
     def rope_for(self, cache0, T: int, device):
         """(cos, sin, offset) for this forward; handles graph-pos mode
-        (device position tensor) and the eager python-offset mode."""
+        (device position tensor) and the eager python-offset mode.  A
+        [B] position gives per-sequence [B, 1, D/2] tables."""
         gp = cache0.graph_pos if cache0 is not None else None
         if gp is not None:
             cos_t, sin_t = self._rope_tables(device, cache0.capacity)
             idx = gp.to(torch.long)
-            return cos_t.index_select(0, idx), sin_t.index_select(0, idx), 0
+            cos, sin = cos_t.index_select(0, idx), sin_t.index_select(0, idx)
+            if idx.numel() > 1:
+                cos, sin = cos.unsqueeze(1), sin.unsqueeze(1)
+            return cos, sin, 0
         offset = cache0.offset if cache0 is not None else 0
         cos_t, sin_t = self._rope_tables(device, offset + T)
         return cos_t[offset: offset + T], sin_t[offset: offset + T], offset

@@ -109,6 +109,8 @@ def attention(q, k, v, scale: float, causal_offset: int = 0,
     path).  Decode (Tq == 1) runs the hand-written flash-decode kernel;
     ``pos_dev`` (int32 [1] on device) switches it to graph-capture mode:
     k/v are FULL cache buffers and the kernel reads S = pos+1 on device.
+    An int32 [B] ``pos_dev`` is ragged batched decode: row b attends over
+    its own first pos[b]+1 keys.
     Prefill composes hipBLASLt batch GEMMs with fp32 softmax.
     """
     if _use_hip(q):
@@ -124,6 +126,14 @@ def attention(q, k, v, scale: float, causal_offset: int = 0,
         return _prefill_attention_gpu(q, k, v, scale, causal_offset,
                                       softcap, sliding_window)
     if pos_dev is not None:  # CPU fallback for tests of the graph path
+        if pos_dev.numel() > 1:
+            outs = []
+            for b, p in enumerate(pos_dev.tolist()):
+                outs.append(ref.attention(
+                    q[b:b + 1], k[b:b + 1, :, :p + 1], v[b:b + 1, :, :p + 1],
+                    scale, causal_offset=p, softcap=softcap,
+                    sliding_window=sliding_window))
+            return torch.cat(outs, dim=0)
         S = int(pos_dev.item()) + 1
         return ref.attention(q, k[:, :, :S], v[:, :, :S], scale,
                              causal_offset=S - 1, softcap=softcap,

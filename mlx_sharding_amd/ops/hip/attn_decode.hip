@@ -3,7 +3,9 @@
 //
 // Shapes: q [B, Hq, 1, Dk], kcache [B, Hkv, Scap, Dk], vcache
 // [B, Hkv, Scap, Dv]; S = valid length (host int or device pos+1 for
-// hipGraph capture).  GQA: one block serves one (batch, kv-head) pair
+// hipGraph capture; the device position is one value for the whole
+// batch or one per batch row — ragged continuous-batching decode).
+// GQA: one block serves one (batch, kv-head) pair
 // and computes all G = Hq/Hkv query heads at once, so each K/V byte is
 // read once regardless of the GQA ratio.  Supports MLA shapes (Dk=192,
 // Dv=128), gemma2 softcap + sliding window.  fp32 accumulation, online
@@ -35,11 +37,14 @@ __global__ __launch_bounds__(AD_BLOCK) void attn_decode_kernel(
     short* __restrict__ out,          // [B, Hq, Dv]      (nsplit == 1)
     float* __restrict__ part_o,       // [B, Hkv, G, NS, Dv]  (nsplit > 1)
     float* __restrict__ part_ml,      // [B, Hkv, G, NS, 2]
-    const int* __restrict__ s_ptr,    // device position (S = *s_ptr + 1), or null
+    const int* __restrict__ s_ptr,    // device position(s), or null
+    int s_bstride,                    // 0: one shared position, 1: s_ptr[b]
     int B, int Hq, int Hkv, int S, long Scap, int Dk, int Dv, long vstride,
     float scale, float softcap, int window) {
-  if (s_ptr) S = *s_ptr + 1;  // hipGraph-captured decode: length lives on device
   const int b = blockIdx.x / Hkv;
+  // hipGraph-captured decode: length lives on device (block-uniform, so
+  // the load stays scalar); row b is at s_ptr[b] when s_bstride == 1
+  if (s_ptr) S = s_ptr[b * s_bstride] + 1;
   const int hk = blockIdx.x % Hkv;
   const int split = blockIdx.y;
   const int nsplit = gridDim.y;
@@ -293,7 +298,8 @@ __global__ void attn_decode_combine_kernel(
 
 extern "C" void launch_attn_decode(const void* q, const void* k, const void* v,
                                    void* out, float* part_o, float* part_ml,
-                                   int nsplit, const int* s_ptr, int B, int Hq,
+                                   int nsplit, const int* s_ptr,
+                                   int s_bstride, int B, int Hq,
                                    int Hkv, int S, long Scap, int Dk, int Dv,
                                    long vstride, float scale, float softcap,
                                    int window, hipStream_t stream) {
@@ -315,8 +321,8 @@ extern "C" void launch_attn_decode(const void* q, const void* k, const void* v,
   case GG * 16 + VT:                                                         \
     attn_decode_kernel<GG, VT><<<grid, block, smem, stream>>>(               \
         (const short*)q, (const short*)k, (const short*)v, (short*)out,      \
-        part_o, part_ml, s_ptr, B, Hq, Hkv, S, Scap, Dk, Dv, vstride, scale, \
-        softcap, window);                                                    \
+        part_o, part_ml, s_ptr, s_bstride, B, Hq, Hkv, S, Scap, Dk, Dv,      \
+        vstride, scale, softcap, window);                                    \
     break;
   switch (G * 16 + DVT) {
     AD_CASE(1, 1)

@@ -18,17 +18,17 @@ void launch_glu_strided(const void*, const void*, void*, long, int, long,
                         long, bool, hipStream_t);
 void launch_softcap(const void*, void*, long, float, hipStream_t);
 void launch_rope(const void*, void*, const float*, const float*, long, int,
-                 int, int, bool, long, long, hipStream_t);
+                 int, int, bool, long, long, long, hipStream_t);
 void launch_mla_append_kv(const void*, const void*, void*, void*, const int*,
-                          int, int, int, int, int, int, int, long, long,
+                          int, int, int, int, int, int, int, int, long, long,
                           hipStream_t);
 void launch_rope_append_kv(const void*, const void*, const float*,
                            const float*, void*, void*, const int*, int, int,
-                           int, int, int, long, bool, long, long,
+                           int, int, int, int, long, bool, long, long, long,
                            hipStream_t);
 void launch_attn_decode(const void*, const void*, const void*, void*, float*,
-                        float*, int, const int*, int, int, int, int, long,
-                        int, int, long, float, float, int, hipStream_t);
+                        float*, int, const int*, int, int, int, int, int,
+                        long, int, int, long, float, float, int, hipStream_t);
 bool attn_decode_supported_shape(int, int);
 void launch_attn_prefill(const void*, const void*, const void*, void*, int,
                          int, int, int, int, long, long, int, int, float,
@@ -129,6 +129,40 @@ torch::Tensor splitk_scratch(int nk, int M, int O,
   return torch::empty({M, O}, opts.dtype(torch::kFloat32));
 }
 
+// Device decode position: int32 [1] (every batch row at the same
+// position) or int32 [B] (row b at pos[b] — ragged batched decode).
+// Returns the pointer and sets the per-row element stride (0 or 1).
+const int* pos_arg(const c10::optional<torch::Tensor>& pos, int B,
+                   int& bstride) {
+  bstride = 0;
+  if (!pos.has_value()) return nullptr;
+  TORCH_CHECK(pos->is_cuda() && pos->scalar_type() == torch::kInt32 &&
+                  pos->is_contiguous(),
+              "pos must be a contiguous int32 GPU tensor");
+  const long n = pos->numel();
+  TORCH_CHECK(n == 1 || n == B, "pos must hold 1 or B=", B,
+              " positions, got ", n);
+  bstride = (n == 1) ? 0 : 1;
+  return pos->data_ptr<int>();
+}
+
+// cos/sin tables: [T, D/2] shared by every batch row, or [B, T, D/2]
+// per sequence.  Returns the per-row element stride (0 when shared).
+long rope_table_bstride(const torch::Tensor& cc, const torch::Tensor& sc,
+                        int B, int T, int half) {
+  TORCH_CHECK(cc.scalar_type() == torch::kFloat32 &&
+                  sc.scalar_type() == torch::kFloat32, "cos/sin must be fp32");
+  TORCH_CHECK(sc.sizes() == cc.sizes(), "cos/sin shape mismatch");
+  if (cc.dim() == 3) {
+    TORCH_CHECK(cc.size(0) == B && cc.size(1) == T && cc.size(2) == half,
+                "cos shape mismatch: want [B, T, D/2]");
+    return (long)T * half;
+  }
+  TORCH_CHECK(cc.dim() == 2 && cc.size(0) == T && cc.size(1) == half,
+              "cos shape mismatch: want [T, D/2]");
+  return 0;
+}
+
 float* f32_or_null(const torch::Tensor& t) {
   return t.defined() ? t.data_ptr<float>() : nullptr;
 }
@@ -206,16 +240,15 @@ torch::Tensor softcap_op(torch::Tensor x, double cap) {
   return y;
 }
 
-// x: [B, T, nH, D]; cos/sin: [T, D/2] fp32
+// x: [B, T, nH, D]; cos/sin: [T, D/2] or [B, T, D/2] fp32
 torch::Tensor apply_rope(torch::Tensor x, torch::Tensor cos, torch::Tensor sin,
                          bool interleaved) {
   check_bf16(x, "x");
   TORCH_CHECK(x.dim() == 4, "x must be [B, T, nH, D]");
   auto cc = cos.contiguous();
   auto sc = sin.contiguous();
-  TORCH_CHECK(cc.scalar_type() == torch::kFloat32, "cos must be fp32");
   const int B = x.size(0), T = x.size(1), nH = x.size(2), D = x.size(3);
-  TORCH_CHECK(cc.size(0) == T && cc.size(1) == D / 2, "cos shape mismatch");
+  const long csb = rope_table_bstride(cc, sc, B, T, D / 2);
   // fused-qkv splits / nope-rope slices read in place
   torch::Tensor xv = x;
   long rstride = (long)nH * D, hstride = D;
@@ -230,7 +263,7 @@ torch::Tensor apply_rope(torch::Tensor x, torch::Tensor cos, torch::Tensor sin,
   auto y = torch::empty({B, T, nH, D}, x.options());
   launch_rope(xv.data_ptr(), y.data_ptr(), cc.data_ptr<float>(),
               sc.data_ptr<float>(), (long)B * T, T, nH, D, interleaved,
-              rstride, hstride, cur_stream());
+              rstride, hstride, csb, cur_stream());
   return y;
 }
 
@@ -243,16 +276,15 @@ void rope_append_kv(torch::Tensor k, torch::Tensor v, torch::Tensor cos,
   TORCH_CHECK(k.dim() == 4, "k must be [B, T, Hkv, D]");
   auto cc = cos.contiguous();
   auto sc = sin.contiguous();
-  TORCH_CHECK(cc.scalar_type() == torch::kFloat32, "cos must be fp32");
   const int B = k.size(0), T = k.size(1), Hkv = k.size(2), D = k.size(3);
   TORCH_CHECK(D % 2 == 0, "head dim must be even");
-  TORCH_CHECK(cc.size(0) == T && cc.size(1) == D / 2, "cos shape mismatch");
+  const long csb = rope_table_bstride(cc, sc, B, T, D / 2);
   TORCH_CHECK(kcache.is_contiguous() && vcache.is_contiguous(),
               "caches contiguous");
   TORCH_CHECK(kcache.size(3) == D && vcache.size(3) == D, "cache D mismatch");
   const long Scap = kcache.size(2);
-  const int* pp = nullptr;
-  if (pos.has_value()) pp = pos->data_ptr<int>();
+  int pbs;
+  const int* pp = pos_arg(pos, B, pbs);
   // fused-qkv split views read in place (heads contiguous within slice)
   auto view_ok = [&](const torch::Tensor& t) {
     return t.stride(3) == 1 && t.stride(2) == D
@@ -264,8 +296,8 @@ void rope_append_kv(torch::Tensor k, torch::Tensor v, torch::Tensor cos,
   if (view_ok(v)) vrs = v.stride(1); else vv = v.contiguous();
   launch_rope_append_kv(kv.data_ptr(), vv.data_ptr(), cc.data_ptr<float>(),
                         sc.data_ptr<float>(), kcache.data_ptr(),
-                        vcache.data_ptr(), pp, (int)pos0, B, T, Hkv, D, Scap,
-                        interleaved, krs, vrs, cur_stream());
+                        vcache.data_ptr(), pp, pbs, (int)pos0, B, T, Hkv, D,
+                        Scap, interleaved, krs, vrs, csb, cur_stream());
 }
 
 // kvh [B, T, nh, nope+vd]; kpe [B, T, rope]; caches full buffers
@@ -281,8 +313,8 @@ void mla_append_kv(torch::Tensor kvh, torch::Tensor kpe, torch::Tensor kcache,
   TORCH_CHECK(kvh.size(3) == nope + vd, "kvh dim mismatch");
   TORCH_CHECK(kcache.is_contiguous() && vcache.is_contiguous(), "caches contiguous");
   const long Scap = kcache.size(2);
-  const int* pp = nullptr;
-  if (pos.has_value()) pp = pos->data_ptr<int>();
+  int pbs;
+  const int* pp = pos_arg(pos, B, pbs);
   long kpe_rows, kpe_rs;
   torch::Tensor kpev = kpe;
   if (!row_view2(kpe, kpe_rows, kpe_rs)) {
@@ -290,8 +322,9 @@ void mla_append_kv(torch::Tensor kvh, torch::Tensor kpe, torch::Tensor kcache,
     kpe_rs = rope;
   }
   launch_mla_append_kv(kvh.contiguous().data_ptr(), kpev.data_ptr(),
-                       kcache.data_ptr(), vcache.data_ptr(), pp, (int)pos0, B,
-                       T, nh, nope, vd, rope, Scap, kpe_rs, cur_stream());
+                       kcache.data_ptr(), vcache.data_ptr(), pp, pbs,
+                       (int)pos0, B, T, nh, nope, vd, rope, Scap, kpe_rs,
+                       cur_stream());
 }
 
 // q [B, Hq, 1, Dk]; k/v: cache views [B, Hkv, S, D] with row-contiguous
@@ -320,11 +353,8 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   long vScap = v.stride(1) / vstride;
   TORCH_CHECK(kScap == vScap, "K/V capacity mismatch");
   auto out = torch::empty({B, Hq, 1, Dv}, qc.options());
-  const int* s_ptr = nullptr;
-  if (pos.has_value()) {
-    TORCH_CHECK(pos->scalar_type() == torch::kInt32, "pos must be int32");
-    s_ptr = pos->data_ptr<int>();
-  }
+  int sbs;
+  const int* s_ptr = pos_arg(pos, B, sbs);
   // split-S for parallelism: target ~1024 blocks, slices of >= 512 keys
   // (>= 256 keys when B*Hkv alone leaves the chip block-starved, e.g.
   // absorbed MLA with Hkv = 1)
@@ -344,8 +374,8 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
     part_ml = pml.data_ptr<float>();
   }
   launch_attn_decode(qc.data_ptr(), k.data_ptr(), v.data_ptr(),
-                     out.data_ptr(), part_o, part_ml, nsplit, s_ptr, B, Hq,
-                     Hkv, S, kScap, Dk, Dv, vstride, (float)scale,
+                     out.data_ptr(), part_o, part_ml, nsplit, s_ptr, sbs, B,
+                     Hq, Hkv, S, kScap, Dk, Dv, vstride, (float)scale,
                      (float)softcap, (int)window, cur_stream());
   return out;
 }

@@ -215,7 +215,8 @@ extern "C" void launch_softcap(const void* x, void* y, long n, float cap,
 
 // ---------------------------------------------------------------------------
 // RoPE: x [rows=B*T, n_heads, D], cos/sin [T, D/2] fp32 (host-precomputed
-// tables — guide Appendix B: never sinf/cosf per element on device).
+// tables — guide Appendix B: never sinf/cosf per element on device), or
+// [B, T, D/2] per-sequence tables (cs_bstride = T*D/2; 0 when shared).
 // Half-split (llama) or interleaved (deepseek rope slice).
 // One thread per (row, head, pair).
 // ---------------------------------------------------------------------------
@@ -225,7 +226,7 @@ __global__ void rope_kernel(const short* __restrict__ x, short* __restrict__ y,
                             const float* __restrict__ cost,
                             const float* __restrict__ sint,
                             int T, int n_heads, int D, long xrstride,
-                            int xhstride) {
+                            int xhstride, long cs_bstride) {
   const int half = D / 2;
   const long bh = blockIdx.x;
   const long row = bh / n_heads;
@@ -234,8 +235,9 @@ __global__ void rope_kernel(const short* __restrict__ x, short* __restrict__ y,
   // x may be a strided view (fused-qkv split / nope-rope slice)
   const short* xr = x + row * xrstride + (long)head * xhstride;
   short* yr = y + (row * n_heads + head) * D;
-  const float* c = cost + (long)t * half;
-  const float* s = sint + (long)t * half;
+  const long cs_off = (row / T) * cs_bstride + (long)t * half;
+  const float* c = cost + cs_off;
+  const float* s = sint + cs_off;
   for (int p = threadIdx.x; p < half; p += blockDim.x) {
     float x1, x2;
     int i1, i2;
@@ -258,17 +260,18 @@ __global__ void rope_kernel(const short* __restrict__ x, short* __restrict__ y,
 extern "C" void launch_rope(const void* x, void* y, const float* cost,
                             const float* sint, long rows, int T, int n_heads,
                             int D, bool interleaved, long xrstride,
-                            long xhstride, hipStream_t stream) {
+                            long xhstride, long cs_bstride,
+                            hipStream_t stream) {
   dim3 grid((unsigned)(rows * n_heads));
   int block = D / 2 < 64 ? 64 : (D / 2 > 256 ? 256 : D / 2);
   if (interleaved)
     rope_kernel<true><<<grid, dim3(block), 0, stream>>>(
         (const short*)x, (short*)y, cost, sint, T, n_heads, D, xrstride,
-        (int)xhstride);
+        (int)xhstride, cs_bstride);
   else
     rope_kernel<false><<<grid, dim3(block), 0, stream>>>(
         (const short*)x, (short*)y, cost, sint, T, n_heads, D, xrstride,
-        (int)xhstride);
+        (int)xhstride, cs_bstride);
 }
 
 // ---------------------------------------------------------------------------
@@ -278,19 +281,21 @@ extern "C" void launch_rope(const void* x, void* y, const float* cost,
 // kvh  [B, T, nh, nope+vd]  (contiguous kv_b_proj output)
 // kpe  [B, T, rope]         (roped shared key slice)
 // kcache [B, nh, Scap, nope+rope]; vcache [B, nh, Scap, vd]
-// position = *pos_ptr (graph mode) or pos0, plus the row's t.
+// position = pos_ptr[b * pos_bstride] (graph mode: one shared position
+// with stride 0, one per batch row with stride 1) or pos0, plus the
+// row's t.
 // ---------------------------------------------------------------------------
 
 __global__ void mla_append_kv_kernel(
     const short* __restrict__ kvh, const short* __restrict__ kpe,
     short* __restrict__ kcache, short* __restrict__ vcache,
-    const int* __restrict__ pos_ptr, int pos0, int B, int T, int nh,
-    int nope, int vd, int rope, long Scap, long kpe_rstride) {
+    const int* __restrict__ pos_ptr, int pos_bstride, int pos0, int B, int T,
+    int nh, int nope, int vd, int rope, long Scap, long kpe_rstride) {
   const int bh = blockIdx.x;
   const int t = blockIdx.y;
   const int b = bh / nh;
   const int h = bh % nh;
-  const long pos = (pos_ptr ? *pos_ptr : pos0) + t;
+  const long pos = (pos_ptr ? pos_ptr[b * pos_bstride] : pos0) + t;
   const short* src = kvh + (((long)b * T + t) * nh + h) * (nope + vd);
   const short* pe = kpe + ((long)b * T + t) * kpe_rstride;  // may be a slice view
   short* krow = kcache + (((long)b * nh + h) * Scap + pos) * (nope + rope);
@@ -304,7 +309,8 @@ __global__ void mla_append_kv_kernel(
 // Fused GQA rope-k + KV-cache append: applies RoPE to the new k rows and
 // scatters k/v straight into the caches — replaces a rope launch plus
 // two index_copy launches per layer on the llama/gemma decode path.
-// k/v [B, T, Hkv, D] (contiguous), caches [B, Hkv, Scap, D].
+// k/v [B, T, Hkv, D] (contiguous), caches [B, Hkv, Scap, D].  Position
+// and cos/sin tables are shared or per batch row, as above.
 // ---------------------------------------------------------------------------
 
 template <bool INTERLEAVED>
@@ -312,13 +318,14 @@ __global__ void rope_append_kv_kernel(
     const short* __restrict__ k, const short* __restrict__ v,
     const float* __restrict__ cost, const float* __restrict__ sint,
     short* __restrict__ kcache, short* __restrict__ vcache,
-    const int* __restrict__ pos_ptr, int pos0, int B, int T, int Hkv, int D,
-    long Scap, long k_rstride, long v_rstride) {
+    const int* __restrict__ pos_ptr, int pos_bstride, int pos0, int B, int T,
+    int Hkv, int D, long Scap, long k_rstride, long v_rstride,
+    long cs_bstride) {
   const int bh = blockIdx.x;
   const int t = blockIdx.y;
   const int b = bh / Hkv;
   const int h = bh % Hkv;
-  const long pos = (pos_ptr ? *pos_ptr : pos0) + t;
+  const long pos = (pos_ptr ? pos_ptr[b * pos_bstride] : pos0) + t;
   // k/v may be fused-qkv split views: per-(b,t) row stride differs from
   // Hkv*D but heads stay contiguous within the slice
   const short* kr = k + ((long)b * T + t) * k_rstride + (long)h * D;
@@ -326,8 +333,9 @@ __global__ void rope_append_kv_kernel(
   short* kd = kcache + (((long)b * Hkv + h) * Scap + pos) * D;
   short* vd = vcache + (((long)b * Hkv + h) * Scap + pos) * D;
   const int half = D / 2;
-  const float* c = cost + (long)t * half;
-  const float* s = sint + (long)t * half;
+  const long cs_off = (long)b * cs_bstride + (long)t * half;
+  const float* c = cost + cs_off;
+  const float* s = sint + cs_off;
   for (int p = threadIdx.x; p < half; p += blockDim.x) {
     int i1, i2;
     if (INTERLEAVED) {
@@ -348,33 +356,35 @@ __global__ void rope_append_kv_kernel(
 extern "C" void launch_rope_append_kv(const void* k, const void* v,
                                       const float* cost, const float* sint,
                                       void* kcache, void* vcache,
-                                      const int* pos_ptr, int pos0, int B,
-                                      int T, int Hkv, int D, long Scap,
-                                      bool interleaved, long k_rstride,
-                                      long v_rstride, hipStream_t stream) {
+                                      const int* pos_ptr, int pos_bstride,
+                                      int pos0, int B, int T, int Hkv, int D,
+                                      long Scap, bool interleaved,
+                                      long k_rstride, long v_rstride,
+                                      long cs_bstride, hipStream_t stream) {
   dim3 grid((unsigned)(B * Hkv), (unsigned)T);
   int block = D / 2 < 64 ? 64 : (D / 2 > 256 ? 256 : D / 2);
   if (interleaved)
     rope_append_kv_kernel<true><<<grid, dim3(block), 0, stream>>>(
         (const short*)k, (const short*)v, cost, sint, (short*)kcache,
-        (short*)vcache, pos_ptr, pos0, B, T, Hkv, D, Scap, k_rstride,
-        v_rstride);
+        (short*)vcache, pos_ptr, pos_bstride, pos0, B, T, Hkv, D, Scap,
+        k_rstride, v_rstride, cs_bstride);
   else
     rope_append_kv_kernel<false><<<grid, dim3(block), 0, stream>>>(
         (const short*)k, (const short*)v, cost, sint, (short*)kcache,
-        (short*)vcache, pos_ptr, pos0, B, T, Hkv, D, Scap, k_rstride,
-        v_rstride);
+        (short*)vcache, pos_ptr, pos_bstride, pos0, B, T, Hkv, D, Scap,
+        k_rstride, v_rstride, cs_bstride);
 }
 
 extern "C" void launch_mla_append_kv(const void* kvh, const void* kpe,
                                      void* kcache, void* vcache,
-                                     const int* pos_ptr, int pos0, int B,
-                                     int T, int nh, int nope, int vd, int rope,
-                                     long Scap, long kpe_rstride,
-                                     hipStream_t stream) {
+                                     const int* pos_ptr, int pos_bstride,
+                                     int pos0, int B, int T, int nh, int nope,
+                                     int vd, int rope, long Scap,
+                                     long kpe_rstride, hipStream_t stream) {
   mla_append_kv_kernel<<<dim3((unsigned)(B * nh), (unsigned)T), dim3(128), 0,
                          stream>>>((const short*)kvh, (const short*)kpe,
                                    (short*)kcache, (short*)vcache, pos_ptr,
-                                   pos0, B, T, nh, nope, vd, rope, Scap,
+                                   pos_bstride, pos0, B, T, nh, nope, vd,
+                                   rope, Scap,
                                    kpe_rstride);
 }

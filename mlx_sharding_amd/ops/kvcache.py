@@ -36,9 +36,14 @@ class KVCache:
         self.offset = 0
         self._k: Optional[torch.Tensor] = None
         self._v: Optional[torch.Tensor] = None
-        # hipGraph-captured decode: position lives on device (int32 [1]);
-        # update() appends by index_copy_ and python offset is not advanced.
+        # hipGraph-captured decode: position lives on device (int32 [1],
+        # or int32 [B] with row b at pos[b] — ragged batched decode);
+        # update() appends by index and python offset is not advanced.
         self.graph_pos: Optional[torch.Tensor] = None
+        # fixed-capacity mode (slot pools and their views): never
+        # reallocate — a view that grew would silently detach from the
+        # pool — so running past the capacity raises instead
+        self._fixed = False
 
     def _ensure(self, batch: int, needed: int):
         cap = 0 if self._k is None else self._k.shape[2]
@@ -46,6 +51,9 @@ class KVCache:
             raise ValueError(f"KV cache batch mismatch: {self._k.shape[0]} vs {batch}")
         if needed <= cap and self._k is not None:
             return
+        if self._fixed:
+            raise ValueError(f"KV cache capacity {cap} is fixed; "
+                             f"{needed} positions needed")
         new_cap = ((needed + self.CHUNK - 1) // self.CHUNK) * self.CHUNK
         nk = torch.empty(batch, self.n_kv_heads, new_cap, self.k_head_dim,
                          dtype=self.dtype, device=self.device)
@@ -65,6 +73,11 @@ class KVCache:
         device (capture-safe: no python-int shapes)."""
         if self.graph_pos is not None:
             idx = self.graph_pos.to(torch.long)
+            if idx.numel() > 1:  # per-row positions: row b lands at pos[b]
+                rows = torch.arange(idx.numel(), device=idx.device)
+                self._k[rows, :, idx] = k[:, :, 0]
+                self._v[rows, :, idx] = v[:, :, 0]
+                return self._k, self._v
             self._k.index_copy_(2, idx, k)
             self._v.index_copy_(2, idx, v)
             return self._k, self._v
@@ -135,6 +148,31 @@ class KVCache:
         b = batch if batch is not None else (
             self._k.shape[0] if self._k is not None else self.batch_size)
         self._ensure(b, cap)
+
+    def allocate(self, capacity: int, batch: Optional[int] = None):
+        """Allocate exactly ``capacity`` positions and fix the size: the
+        slot pool of continuous batching (one row per sequence)."""
+        b = batch if batch is not None else self.batch_size
+        shape = (b, self.n_kv_heads, capacity)
+        self._k = torch.zeros(*shape, self.k_head_dim, dtype=self.dtype,
+                              device=self.device)
+        self._v = torch.zeros(*shape, self.v_head_dim, dtype=self.dtype,
+                              device=self.device)
+        self.batch_size = b
+        self._fixed = True
+
+    def slot(self, i: int) -> "KVCache":
+        """B=1 cache over row ``i`` of this pool's buffers: own offset,
+        fixed capacity (appending past it raises).  A row slice of a
+        contiguous pool is itself contiguous, so prefill kernels run
+        against it unmodified."""
+        if self._k is None or not 0 <= i < self._k.shape[0]:
+            raise IndexError(f"slot {i} outside the allocated pool")
+        c = KVCache(self.n_kv_heads, self.k_head_dim, self.v_head_dim,
+                    dtype=self.dtype, device=self.device, batch_size=1)
+        c._k, c._v = self._k[i:i + 1], self._v[i:i + 1]
+        c._fixed = True
+        return c
 
     def trim(self, n: int):
         """Roll back to the first ``n`` cached positions (prefix-cache

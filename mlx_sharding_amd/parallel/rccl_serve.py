@@ -181,6 +181,21 @@ class RcclModelProvider:
         self.tokenizer = tokenizer
         self.model = pipeline.worker.model
         self.remotes = []
+        # continuous batching (--max-batch N > 1, single stage only):
+        # requests go to one BatchScheduler instead of the locked B=1
+        # pipeline loop
+        from .batching import BatchScheduler, max_batch_of, serve_capacity
+        self.max_batch = max_batch_of(cli_args)
+        self._scheduler = None
+        if self.max_batch > 1:
+            if pipeline.worker.world > 1:
+                raise ValueError("--max-batch > 1 needs a single-stage "
+                                 "pipeline (world size 1)")
+            self._scheduler = BatchScheduler(
+                self.model, self.max_batch, serve_capacity(),
+                pipeline.device,
+                prefill_chunk=int(os.environ.get("MLXS_PREFILL_CHUNK", "0")))
+            self.check_prompt = self._scheduler.check_prompt
 
     def load(self, model_path: str):
         # hot-swap is not supported across a live pipeline; serve the
@@ -188,5 +203,7 @@ class RcclModelProvider:
         return self.model, self.tokenizer
 
     def generate(self, prompt_ids: List[int], params: SamplingParams):
+        if self._scheduler is not None:
+            return self._scheduler.submit(prompt_ids, params)
         ids = torch.tensor([prompt_ids], dtype=torch.long)
         return self.pipeline.generate_step(ids, params)

@@ -104,6 +104,19 @@ class ModelProvider:
         # shares a prefix re-uses those K/V rows (take/store under the
         # lock — a concurrent second request simply runs fresh)
         self._prefix_state: Optional[Tuple[List[int], list]] = None
+        # continuous batching (--max-batch N > 1): one BatchScheduler per
+        # loaded model backs ``generate``, which APIHandler._gen prefers;
+        # with 1 nothing is constructed and ``generate`` does not exist
+        from ..parallel.batching import max_batch_of
+        self.max_batch = max_batch_of(cli_args)
+        self._scheduler = None
+        if self.max_batch > 1:
+            if self.remotes:
+                raise ValueError(
+                    "--max-batch > 1 batches on one single-stage model; it "
+                    "cannot be combined with --llm-shard-addresses")
+            self.generate = self._generate_batched
+            self.check_prompt = self._check_prompt_batched
         if cli_args.model is not None:
             self.load("default_model")
 
@@ -115,6 +128,12 @@ class ModelProvider:
     def store_prefix_state(self, tokens: List[int], cache: list):
         with self.lock:
             self._prefix_state = (tokens, cache)
+
+    def _generate_batched(self, prompt_ids: List[int], params):
+        return self._scheduler.submit(prompt_ids, params)
+
+    def _check_prompt_batched(self, n_tokens: int):
+        self._scheduler.check_prompt(n_tokens)
 
     def _validate_model_path(self, model_path: str):
         model_path = Path(model_path)
@@ -150,6 +169,15 @@ class ModelProvider:
             device = "cuda" if torch.cuda.is_available() else "cpu"
             model, _config = load_model(path, self.args.start_layer,
                                         self.args.end_layer, device=device)
+            if self.max_batch > 1:
+                from ..parallel.batching import (BatchScheduler,
+                                                 serve_capacity)
+                if self._scheduler is not None:
+                    self._scheduler.close()
+                self._scheduler = BatchScheduler(
+                    model, self.max_batch, serve_capacity(), device,
+                    prefill_chunk=int(os.environ.get("MLXS_PREFILL_CHUNK",
+                                                     "0")))
             self.model_key = model_path
             self.model = model
             self.tokenizer = tokenizer
@@ -257,6 +285,13 @@ class APIHandler(BaseHTTPRequestHandler):
             object_type = "text_completion"
 
         prompt_ids = tokenizer.encode(prompt)
+        check = getattr(self.provider, "check_prompt", None)
+        if check is not None:  # batching: the prompt must fit one slot
+            try:
+                check(len(prompt_ids))
+            except ValueError as e:
+                self._error(400, str(e))
+                return
         stop_words = params["stop"]
         stop_id_sequences = [tokenizer.encode(sw, add_special_tokens=False)
                              for sw in stop_words]
@@ -588,6 +623,12 @@ def main(argv=None):
     p.add_argument("--use-default-chat-template", action="store_true")
     p.add_argument("--static-dir", type=str, default=None,
                    help="directory for web-UI static files")
+    from ..parallel.batching import env_max_batch
+    p.add_argument("--max-batch", type=int, default=env_max_batch(),
+                   help="continuous batching: decode up to N concurrent "
+                        "requests in one batched step (default "
+                        "MLXS_MAX_BATCH or 1 = off; single-stage only; "
+                        "MLXS_PREFIX_CACHE is ignored while batching)")
     p.add_argument("--log-level", type=str, default="INFO",
                    choices=["DEBUG", "INFO", "WARNING", "ERROR", "CRITICAL"])
     args = p.parse_args(argv)
@@ -602,7 +643,10 @@ def main(argv=None):
         total = torch.cuda.get_device_properties(0).total_memory
         torch.cuda.set_per_process_memory_fraction(
             min(1.0, args.cache_limit_gb * (1 << 30) / total))
-    provider = ModelProvider(args)
+    try:
+        provider = ModelProvider(args)
+    except ValueError as e:
+        p.error(str(e))
     server = run(args.host, args.port, provider)
     print(f"API server listening on {args.host}:{server.server_address[1]}", flush=True)
     server.serve_forever()

@@ -131,6 +131,28 @@ class Counter:
                 f"{self.name} {self._v:g}\n")
 
 
+class Gauge:
+    """A value that goes up and down (occupancy, queue depth)."""
+
+    def __init__(self, name: str, help_: str):
+        self.name, self.help = name, help_
+        self._v = 0.0
+        self._lock = threading.Lock()
+
+    def set(self, v: float):
+        with self._lock:
+            self._v = float(v)
+
+    @property
+    def value(self) -> float:
+        return self._v
+
+    def render(self) -> str:
+        return (f"# HELP {self.name} {self.help}\n"
+                f"# TYPE {self.name} gauge\n"
+                f"{self.name} {self._v:g}\n")
+
+
 class Histogram:
     """Fixed-bucket histogram (Prometheus cumulative-bucket semantics)."""
 
@@ -187,6 +209,13 @@ class Registry:
                 m = self._metrics[name] = Counter(name, help_)
             return m  # type: ignore[return-value]
 
+    def gauge(self, name: str, help_: str = "") -> Gauge:
+        with self._lock:
+            m = self._metrics.get(name)
+            if m is None:
+                m = self._metrics[name] = Gauge(name, help_)
+            return m  # type: ignore[return-value]
+
     def histogram(self, name: str, help_: str = "",
                   buckets: Optional[Tuple[float, ...]] = None) -> Histogram:
         with self._lock:
@@ -222,4 +251,17 @@ def serving_metrics(reg: Optional[Registry] = None):
             "mlxs_decode_tokens_per_s", "per-request decode throughput",
             buckets=(1, 5, 10, 25, 50, 100, 150, 200, 300, 500, 1000,
                      5000, 20000)),
+    }
+
+
+def batching_metrics(reg: Optional[Registry] = None):
+    """Continuous-batching scheduler metrics (created on first use)."""
+    reg = reg or REGISTRY
+    return {
+        "active_slots": reg.gauge(
+            "mlxs_batch_active_slots", "slots holding a running request"),
+        "queued": reg.gauge(
+            "mlxs_batch_queued_requests", "requests waiting for a free slot"),
+        "decode_steps": reg.counter(
+            "mlxs_batch_decode_steps_total", "batched decode steps run"),
     }
