@@ -547,6 +547,10 @@ torch::Tensor moe_gateup_grouped(torch::Tensor x, torch::Tensor gate_w,
         cur_stream());
   } else {
     TORCH_CHECK(max_tok <= 4, "scalar grouped kernel needs max_tok <= 4");
+    // the kernel reads weights 8 elements at a time and stages x in 4s
+    TORCH_CHECK(H % 8 == 0 && I % 8 == 0,
+                "scalar grouped kernel needs H % 8 == 0 and I % 8 == 0 (got H=",
+                H, ", I=", I, ")");
     launch_moe_gateup_grouped(
         x.contiguous().data_ptr(), gate_w.data_ptr(), up_w.data_ptr(),
         h.data_ptr(), sub_expert.data_ptr<int>(), sub_off.data_ptr<int>(),
@@ -573,6 +577,10 @@ torch::Tensor moe_down_grouped(torch::Tensor h, torch::Tensor down_w,
         sorted_wt.data_ptr<float>(), S, I, H, cur_stream());
   } else {
     TORCH_CHECK(max_tok <= 4, "scalar grouped kernel needs max_tok <= 4");
+    // the kernel reads weights 8 elements at a time and has no tail loop
+    TORCH_CHECK(H % 8 == 0 && I % 8 == 0,
+                "scalar grouped kernel needs H % 8 == 0 and I % 8 == 0 (got H=",
+                H, ", I=", I, ")");
     launch_moe_down_grouped(
         h.contiguous().data_ptr(), down_w.data_ptr(), out.data_ptr<float>(),
         sub_expert.data_ptr<int>(), sub_off.data_ptr<int>(),
@@ -592,6 +600,9 @@ torch::Tensor moe_w4_mfma(torch::Tensor x, torch::Tensor wq,
   const int O = wq.size(1);
   const int S = sub_expert.size(0);
   TORCH_CHECK(H % 32 == 0 && gs % 32 == 0, "H%32, gs%32 required");
+  // a partial last group would index past the row's H / gs scales
+  TORCH_CHECK(H % gs == 0, "moe_w4_mfma needs H % gs == 0 (got H=", H,
+              ", gs=", gs, ")");
   auto y = torch::empty({P, O}, x.options());
   launch_moe_w4_mfma(x.contiguous().data_ptr(), wq.data_ptr(),
                      scales.data_ptr(), biases.data_ptr(), y.data_ptr(),
@@ -742,6 +753,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe", &mfma_probe);
   m.def("w4a16_gemv", &w4a16_gemv);
   m.def("w4f16_gemv", &w4f16_gemv);
+  // split-K factors the two quantized GEMV bindings will use (tests pin
+  // which store path a shape takes)
+  m.def("w4a16_mfma_nsplit", [](int64_t M, int64_t O, int64_t H) {
+    return w4a16_mfma_nsplit((int)M, (int)O, (int)H);
+  });
+  m.def("w4f16_gemv_nsplit", [](int64_t M, int64_t O, int64_t H) {
+    return w4f16_gemv_nsplit((int)M, (int)O, (int)H);
+  });
   m.def("dense_gemv", &dense_gemv);
   m.def("dense_gemm64", &dense_gemm64);
   m.def("gemm_m64_kseg", &gemm_m64_kseg);

@@ -130,7 +130,8 @@ __global__ __launch_bounds__(MG_BLOCK) void moe_down_grouped_kernel(
     const short* drow = down_w + ebase + (long)o * I;
     float dot[MG_TOK] = {};
     // 16 B/lane weight loads (guide G13); v_dot2c accumulate as in the
-    // gate/up kernel.  I % 512 handled by the 8-tail.
+    // gate/up kernel.  There is no tail: the binding requires I % 8 == 0,
+    // and the lane stride covers any such I.
     for (int d = lane * 8; d + 7 < I; d += WAVE * 8) {
       bf16x8_t dv = *reinterpret_cast<const bf16x8_t*>(drow + d);
 #pragma unroll
