@@ -51,8 +51,9 @@ class SwitchMLP(nn.Module):
             self.quant.group_size, self.quant.bits)
 
     def forward_subs(self, x_flat: torch.Tensor, subs,
-                     max_tok: int = 4) -> torch.Tensor:
-        """Run from prebuilt fused-gating sub-range arrays (GPU decode)."""
+                     max_tok: int = 4, raw: bool = False) -> torch.Tensor:
+        """Run from prebuilt fused-gating sub-range arrays (GPU decode).
+        raw: return the fp32 accumulator (for ops.moe_finalize)."""
         if self.quant is not None:
             # the fp16-dequant packed MFMA kernels (moe_w4f16.hip) beat
             # streaming resident bf16 copies (4x less weight traffic,
@@ -64,17 +65,18 @@ class SwitchMLP(nn.Module):
                 dense = self.resident_dense()
                 if dense is not None:
                     return ops.grouped_expert_mlp_subs(
-                        x_flat, dense[0], dense[1], dense[2], subs, max_tok)
+                        x_flat, dense[0], dense[1], dense[2], subs, max_tok,
+                        raw=raw)
             g, u, d = self.gate_proj, self.up_proj, self.down_proj
             return ops.grouped_expert_mlp_quant_subs(
                 x_flat,
                 (g.weight, g.scales, g.biases),
                 (u.weight, u.scales, u.biases),
                 (d.weight, d.scales, d.biases),
-                subs, self.quant.group_size, self.quant.bits)
+                subs, self.quant.group_size, self.quant.bits, raw=raw)
         return ops.grouped_expert_mlp_subs(
             x_flat, self.gate_proj.weight, self.up_proj.weight,
-            self.down_proj.weight, subs, max_tok)
+            self.down_proj.weight, subs, max_tok, raw=raw)
 
     def forward(self, x_flat: torch.Tensor, weights: torch.Tensor,
                 indices: torch.Tensor) -> torch.Tensor:
@@ -215,6 +217,11 @@ class MLAAttention(nn.Module):
         else:
             qh = self.q_proj(x)
         qh = qh.view(B, T, nh, self.qk_head_dim)
+        if (T == 1 and ops.use_native(x) and ops.decode_fuse_enabled()
+                and self.qk_nope % 8 == 0 and rope % 2 == 0):
+            if ckv is None:
+                ckv = self.kv_a_proj_with_mqa(x)
+            return self._decode_fused(qh, ckv, cos, sin, cache)
         q_nope = qh[..., : self.qk_nope]
         q_pe = ops.apply_rope(qh[..., self.qk_nope:], cos, sin,
                               interleaved=True)
@@ -276,6 +283,28 @@ class MLAAttention(nn.Module):
         qf = torch.cat([q_nope, q_pe], dim=-1).transpose(1, 2)
         out = ops.attention(qf, k, v, self.scale, causal_offset=offset)
         return self.o_proj(out.transpose(1, 2).reshape(B, T, -1))
+
+    def _decode_fused(self, qh, ckv, cos, sin, cache: KVCache):
+        """T == 1 absorbed decode with the glue folded into native
+        kernels: one prep launch (rope q_pe, norm c_kv, rope k_pe, cache
+        append, head-major q_nope), attention reading q from the W_UK
+        bmm result and the roped q_pe in place and writing the
+        [nh, B, rank] layout the W_UV bmm consumes."""
+        B = qh.shape[0]
+        nh, rank = self.n_heads, self.kv_lora_rank
+        gp = cache.graph_pos
+        ln = self.kv_a_layernorm
+        q_pe, qn, k_all = cache.mla_decode_prep(
+            qh, ckv, ln.weight, ln.eps, ln.weight_offset, cos, sin,
+            self.qk_rope)
+        self._ensure_absorb(qh.device, qh.dtype)
+        q_abs = torch.bmm(qn, self._w_uk)               # [nh, B, rank]
+        o = ops.hip_ext().attn_decode_split(
+            q_abs.transpose(0, 1), q_pe, k_all, k_all[..., :rank],
+            self.scale, 0.0, 0, gp)                     # [nh, B, rank]
+        ov = torch.bmm(o, self._w_uv)                   # [nh, B, vd]
+        out = ov.view(nh, B, 1, self.v_head_dim).permute(1, 2, 0, 3)
+        return self.o_proj(out.reshape(B, 1, -1))
 
     def _forward_naive(self, x, cos, sin, cache: Optional[KVCache]):
         B, T, _ = x.shape
@@ -370,9 +399,36 @@ class DeepseekV2MoE(nn.Module):
                 and 1 <= topk_group <= n_group
                 and topk_group * (E // n_group) >= K)
 
-    def forward(self, x):
+    def packed_decode(self, n_tokens: int) -> bool:
+        """True when forward() on n_tokens GPU tokens runs the packed
+        fp16-dequant expert kernels (the consumers of an fp16 copy of
+        the input)."""
+        import os
+        return (self.switch_mlp.quant is not None
+                and not os.environ.get("MLXS_AMD_MOE_RESIDENT")
+                and self._fused_gate_ok(n_tokens))
+
+    def forward(self, x, residual=None):
+        """residual (fused T == 1 decode only): return residual + moe(x),
+        finished by one moe_finalize launch."""
         B, T, H = x.shape
         flat = x.reshape(-1, H)
+        if (residual is not None and ops.use_native(flat)
+                and self._fused_gate_ok(flat.shape[0])):
+            f16 = getattr(x, "_mlxs_f16", None)
+            if f16 is not None:  # the norm kernel's fp16 copy follows the view
+                flat._mlxs_f16 = f16.view(-1, H)
+            logits = self.gate(flat.to(self.gate.weight.dtype))
+            n_group, topk_group = self._gate_groups()
+            subs = ops.moe_gate_subranges(logits, self.top_k,
+                                          self.routed_scaling_factor,
+                                          self.norm_topk_prob, max_tok=16,
+                                          n_group=n_group,
+                                          topk_group=topk_group)
+            acc = self.switch_mlp.forward_subs(flat, subs, 16, raw=True)
+            shared = (self.shared_experts(flat)
+                      if self.shared_experts is not None else None)
+            return ops.moe_finalize(acc, shared, residual)
         if (ops.use_native(flat)
                 and self._fused_gate_ok(flat.shape[0])):
             # fused gating: one kernel for softmax+topk+sort+subranges
@@ -421,6 +477,14 @@ class DeepseekV2DecoderLayer(nn.Module):
         attn = self.self_attn(self.input_layernorm(x), cos, sin, cache)
         # fused: h = x + attn; y = rms_norm(h) in one kernel
         pn = self.post_attention_layernorm
+        if (x.shape[1] == 1 and ops.use_native(x)
+                and ops.decode_fuse_enabled()
+                and isinstance(self.mlp, DeepseekV2MoE)
+                and self.mlp._fused_gate_ok(x.shape[0])):
+            y, h = ops.rms_norm_residual(
+                attn, x, pn.weight, pn.eps, pn.weight_offset,
+                want_f16=self.mlp.packed_decode(x.shape[0]))
+            return self.mlp(y, residual=h)
         y, h = ops.rms_norm_residual(attn, x, pn.weight, pn.eps,
                                      pn.weight_offset)
         return h + self.mlp(y)

@@ -84,11 +84,29 @@ def rms_norm(x, weight, eps: float = 1e-5, weight_offset: float = 0.0):
     return ref.rms_norm(x, weight, eps, weight_offset)
 
 
-def rms_norm_residual(x, residual, weight, eps: float = 1e-5, weight_offset: float = 0.0):
-    """Fused h = x + residual; y = rms_norm(h). Returns (y, h)."""
+def decode_fuse_enabled() -> bool:
+    """The fused T == 1 decode glue (mla_decode_prep, two-source
+    attn_decode, fp16 norm output, accumulator clear in gate+up,
+    moe_finalize).  MLXS_AMD_NO_DECODE_FUSE=1 restores the unfused op
+    sequence for A/B in one build."""
+    return not os.environ.get("MLXS_AMD_NO_DECODE_FUSE")
+
+
+def rms_norm_residual(x, residual, weight, eps: float = 1e-5,
+                      weight_offset: float = 0.0, want_f16: bool = False):
+    """Fused h = x + residual; y = rms_norm(h). Returns (y, h).
+
+    want_f16 (GPU only): the same launch also writes y.to(float16),
+    attached to y as ``_mlxs_f16`` where _to_f16_cached finds it — ask
+    for it only where the packed MoE kernels will consume it."""
     if _use_hip(x):
-        y, h = _require_ext("rms_norm_residual").rms_norm_residual(
-            x, residual, weight, eps, weight_offset)
+        ext = _require_ext("rms_norm_residual")
+        if want_f16:
+            y, h, y16 = ext.rms_norm_residual(x, residual, weight, eps,
+                                              weight_offset, True)
+            y._mlxs_f16 = y16
+            return y, h
+        y, h = ext.rms_norm_residual(x, residual, weight, eps, weight_offset)
         return y, h
     h = x + residual
     return ref.rms_norm(h, weight, eps, weight_offset), h
@@ -468,7 +486,17 @@ def moe_gate_subranges(router_logits_bf16, top_k: int,
                                         norm_topk_prob, n_group, topk_group))
 
 
-def grouped_expert_mlp_subs(x, gate_w, up_w, down_w, subs, max_tok: int = 4):
+def moe_finalize(acc, shared, h):
+    """out = h + (acc.to(bf16) + shared) in one launch, bit-identical to
+    the three-op sequence; ``shared`` may be None.  acc is the fp32
+    accumulator the grouped-expert ``raw=True`` calls return."""
+    return _require_ext("moe_finalize").moe_finalize(
+        acc, None if shared is None else shared.reshape(acc.shape),
+        h.reshape(acc.shape)).view(h.shape)
+
+
+def grouped_expert_mlp_subs(x, gate_w, up_w, down_w, subs, max_tok: int = 4,
+                            raw: bool = False):
     """Run the grouped expert MLP from prebuilt sub-range arrays.
 
     max_tok selects the kernel family the sub-ranges were built for:
@@ -481,7 +509,8 @@ def grouped_expert_mlp_subs(x, gate_w, up_w, down_w, subs, max_tok: int = 4):
                                sorted_tok, P, max_tok)
     out = ext.moe_down_grouped(h, down_w, sub_e, sub_off, sub_cnt,
                                sorted_tok, sorted_wt, x.shape[0], max_tok)
-    return out.to(x.dtype)
+    # raw: the fp32 accumulator, for moe_finalize
+    return out if raw else out.to(x.dtype)
 
 
 def _to_f16_cached(x: torch.Tensor) -> torch.Tensor:
@@ -536,7 +565,8 @@ def repack_w4(wq: torch.Tensor, bits: int) -> torch.Tensor:
 
 
 def grouped_expert_mlp_quant_subs(x, gate, up, down, subs,
-                                  group_size: int, bits: int):
+                                  group_size: int, bits: int,
+                                  raw: bool = False):
     """Quantized grouped experts over prebuilt 16-token sub-ranges via
     the fp16-dequant MFMA kernels (moe_w4f16.hip): fused gate+up+SiLU
     in one pass, pk_fma dequant (~16 VALU per 8 weights vs ~36 for the
@@ -553,6 +583,16 @@ def grouped_expert_mlp_quant_subs(x, gate, up, down, subs,
     gq = repack_w4(gate[0], bits)
     uq = repack_w4(up[0], bits)
     dq = repack_w4(down[0], bits)
+    if raw:
+        # the gate+up launch zeroes the down kernel's accumulator (no
+        # fill launch); the caller finishes with moe_finalize
+        hh, acc = ext.moe_w4f16_gateup_acc(
+            x16, gq, uq, gate[1], gate[2], up[1], up[2], sub_e, sub_off,
+            sub_cnt, sorted_tok, P, group_size, bits, x.shape[0],
+            down[0].shape[1])
+        return ext.moe_w4f16_down(hh, dq, down[1], down[2], sub_e, sub_off,
+                                  sub_cnt, sorted_tok, sorted_wt, x.shape[0],
+                                  group_size, bits, acc)
     hh = ext.moe_w4f16_gateup(x16, gq, uq, gate[1], gate[2], up[1], up[2],
                               sub_e, sub_off, sub_cnt, sorted_tok, P,
                               group_size, bits)

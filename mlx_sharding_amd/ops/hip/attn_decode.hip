@@ -31,16 +31,18 @@
 // columns of the K rows themselves (vstride = Dk, vcache = kcache).
 template <int G, int DVT>
 __global__ __launch_bounds__(AD_BLOCK) void attn_decode_kernel(
-    const short* __restrict__ q,      // [B, Hq, Dk]
+    const short* __restrict__ q,      // [B, Hq, Dk - Dr] via (q_bs, q_hs)
+    const short* __restrict__ q_rope, // [B, Hq, Dr] via (qr_bs, qr_hs), or null
     const short* __restrict__ kcache, // [B, Hkv, Scap, Dk]
     const short* __restrict__ vcache, // [B, Hkv, Scap, *] (vstride elems/key)
-    short* __restrict__ out,          // [B, Hq, Dv]      (nsplit == 1)
+    short* __restrict__ out,          // [B, Hq, Dv] via (o_bs, o_hs); nsplit == 1
     float* __restrict__ part_o,       // [B, Hkv, G, NS, Dv]  (nsplit > 1)
     float* __restrict__ part_ml,      // [B, Hkv, G, NS, 2]
     const int* __restrict__ s_ptr,    // device position(s), or null
     int s_bstride,                    // 0: one shared position, 1: s_ptr[b]
     int B, int Hq, int Hkv, int S, long Scap, int Dk, int Dv, long vstride,
-    float scale, float softcap, int window) {
+    float scale, float softcap, int window, int Dr, long q_bs, long q_hs,
+    long qr_bs, long qr_hs, long o_bs, long o_hs) {
   const int b = blockIdx.x / Hkv;
   // hipGraph-captured decode: length lives on device (block-uniform, so
   // the load stays scalar); row b is at s_ptr[b] when s_bstride == 1
@@ -63,9 +65,15 @@ __global__ __launch_bounds__(AD_BLOCK) void attn_decode_kernel(
       smem_raw + (((size_t)G * Dk * sizeof(short) + 15) & ~(size_t)15));
   float* red = p_lds + (size_t)G * AD_BLOCK;                   // [max(G, NW)]
 
+  // q rows come from two sources: the leading Dk - Dr columns from q and
+  // the trailing Dr (rope) columns from q_rope, each with its own
+  // (batch, head) element strides — absorbed MLA passes the W_UK bmm
+  // result and the roped q_pe in place instead of a cat'd copy
+  const int Dn = Dk - Dr;
   for (int i = tid; i < G * Dk; i += AD_BLOCK) {
     int g = i / Dk, d = i % Dk;
-    q_lds[i] = q[((long)b * Hq + h0 + g) * Dk + d];
+    q_lds[i] = d < Dn ? q[b * q_bs + (h0 + g) * q_hs + d]
+                      : q_rope[b * qr_bs + (h0 + g) * qr_hs + d - Dn];
   }
   __syncthreads();
 
@@ -243,7 +251,7 @@ __global__ __launch_bounds__(AD_BLOCK) void attn_decode_kernel(
       for (int u = 0; u < DVT; ++u) {
         const int dv = tid + u * AD_BLOCK;
         if (dv < Dv)
-          ((bf16*)out)[((long)b * Hq + h0 + g) * Dv + dv] =
+          ((bf16*)out)[b * o_bs + (h0 + g) * o_hs + dv] =
               f2bf(acc[g * DVT + u] / l[g]);
       }
     return;
@@ -273,9 +281,10 @@ __global__ __launch_bounds__(AD_BLOCK) void attn_decode_kernel(
 __global__ void attn_decode_combine_kernel(
     const float* __restrict__ part_o,  // [B*Hq, NS, Dv]
     const float* __restrict__ part_ml, // [B*Hq, NS, 2]
-    short* __restrict__ out,           // [B, Hq, Dv]
-    int NS, int Dv) {
+    short* __restrict__ out,           // [B, Hq, Dv] via (o_bs, o_hs)
+    int NS, int Dv, int Hq, long o_bs, long o_hs) {
   const long bh = blockIdx.x;
+  short* orow = out + (bh / Hq) * o_bs + (bh % Hq) * o_hs;
   const int tid = threadIdx.x;
   float mstar = -1e30f;
   for (int s = 0; s < NS; ++s)
@@ -292,17 +301,20 @@ __global__ void attn_decode_combine_kernel(
       const float ms = part_ml[(bh * NS + s) * 2];
       o += part_o[(bh * NS + s) * Dv + d] * __expf(ms - mstar);
     }
-    ((bf16*)out)[bh * Dv + d] = f2bf(o / lsum);
+    ((bf16*)orow)[d] = f2bf(o / lsum);
   }
 }
 
-extern "C" void launch_attn_decode(const void* q, const void* k, const void* v,
+extern "C" void launch_attn_decode(const void* q, const void* q_rope,
+                                   const void* k, const void* v,
                                    void* out, float* part_o, float* part_ml,
                                    int nsplit, const int* s_ptr,
                                    int s_bstride, int B, int Hq,
                                    int Hkv, int S, long Scap, int Dk, int Dv,
                                    long vstride, float scale, float softcap,
-                                   int window, hipStream_t stream) {
+                                   int window, int Dr, long q_bs, long q_hs,
+                                   long qr_bs, long qr_hs, long o_bs,
+                                   long o_hs, hipStream_t stream) {
   const int Gtot = Hq / Hkv;
   const int DVT = (Dv + AD_BLOCK - 1) / AD_BLOCK;
   // Big-G over few KV heads (absorbed MLA): split heads across
@@ -320,9 +332,10 @@ extern "C" void launch_attn_decode(const void* q, const void* k, const void* v,
 #define AD_CASE(GG, VT)                                                      \
   case GG * 16 + VT:                                                         \
     attn_decode_kernel<GG, VT><<<grid, block, smem, stream>>>(               \
-        (const short*)q, (const short*)k, (const short*)v, (short*)out,      \
-        part_o, part_ml, s_ptr, s_bstride, B, Hq, Hkv, S, Scap, Dk, Dv,      \
-        vstride, scale, softcap, window);                                    \
+        (const short*)q, (const short*)q_rope, (const short*)k,              \
+        (const short*)v, (short*)out, part_o, part_ml, s_ptr, s_bstride, B,  \
+        Hq, Hkv, S, Scap, Dk, Dv, vstride, scale, softcap, window, Dr, q_bs, \
+        q_hs, qr_bs, qr_hs, o_bs, o_hs);                                     \
     break;
   switch (G * 16 + DVT) {
     AD_CASE(1, 1)
@@ -342,7 +355,7 @@ extern "C" void launch_attn_decode(const void* q, const void* k, const void* v,
   if (nsplit > 1) {
     attn_decode_combine_kernel<<<dim3((unsigned)(B * Hq)), dim3(128), 0,
                                  stream>>>(part_o, part_ml, (short*)out,
-                                           nsplit, Dv);
+                                           nsplit, Dv, Hq, o_bs, o_hs);
   }
 }
 

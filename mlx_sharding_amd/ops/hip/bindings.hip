@@ -11,8 +11,15 @@ extern "C" {
 void launch_rms_norm(const void*, void*, const void*, long, int, float, float,
                      long, hipStream_t);
 void launch_rms_norm_residual(const void*, const void*, void*, void*,
-                              const void*, long, int, float, float,
+                              const void*, long, int, float, float, void*,
                               hipStream_t);
+void launch_mla_decode_prep(const void*, const void*, const void*,
+                            const float*, const float*, void*, void*, void*,
+                            const int*, int, int, int, int, int, int, int,
+                            long, long, long, long, long, float, float,
+                            hipStream_t);
+void launch_moe_finalize(const float*, const void*, const void*, void*, long,
+                         hipStream_t);
 void launch_glu(const void*, const void*, void*, long, bool, hipStream_t);
 void launch_glu_strided(const void*, const void*, void*, long, int, long,
                         long, bool, hipStream_t);
@@ -26,9 +33,10 @@ void launch_rope_append_kv(const void*, const void*, const float*,
                            const float*, void*, void*, const int*, int, int,
                            int, int, int, int, long, bool, long, long, long,
                            hipStream_t);
-void launch_attn_decode(const void*, const void*, const void*, void*, float*,
-                        float*, int, const int*, int, int, int, int, int,
-                        long, int, int, long, float, float, int, hipStream_t);
+void launch_attn_decode(const void*, const void*, const void*, const void*,
+                        void*, float*, float*, int, const int*, int, int, int,
+                        int, int, long, int, int, long, float, float, int,
+                        int, long, long, long, long, long, long, hipStream_t);
 bool attn_decode_supported_shape(int, int);
 void launch_attn_prefill(const void*, const void*, const void*, void*, int,
                          int, int, int, int, long, long, int, int, float,
@@ -75,7 +83,7 @@ void launch_moe_w4f16_gateup(const void*, const void*, const void*,
                              const void*, const void*, const void*,
                              const void*, void*, const int*, const int*,
                              const int*, const int*, int, int, int, int, int,
-                             hipStream_t);
+                             float*, long, hipStream_t);
 void launch_moe_w4f16_down(const void*, const void*, const void*, const void*,
                            float*, const int*, const int*, const int*,
                            const int*, const float*, int, int, int, int, int,
@@ -187,10 +195,12 @@ torch::Tensor rms_norm(torch::Tensor x, torch::Tensor w, double eps,
   return y;
 }
 
+// with_f16: also return fp16(y) — bit-identical to y.to(float16) — as a
+// third tensor, written by the same launch
 std::vector<torch::Tensor> rms_norm_residual(torch::Tensor x,
                                              torch::Tensor resid,
                                              torch::Tensor w, double eps,
-                                             double w_off) {
+                                             double w_off, bool with_f16) {
   check_bf16(x, "x");
   auto xc = x.contiguous();
   auto rc = resid.contiguous();
@@ -198,10 +208,98 @@ std::vector<torch::Tensor> rms_norm_residual(torch::Tensor x,
   long rows = xc.numel() / H;
   auto y = torch::empty_like(xc);
   auto h = torch::empty_like(xc);
+  torch::Tensor y16;
+  if (with_f16) y16 = torch::empty_like(xc, xc.options().dtype(torch::kHalf));
   launch_rms_norm_residual(xc.data_ptr(), rc.data_ptr(), y.data_ptr(),
                            h.data_ptr(), w.contiguous().data_ptr(), rows, H,
-                           (float)eps, (float)w_off, cur_stream());
+                           (float)eps, (float)w_off,
+                           with_f16 ? y16.data_ptr() : nullptr, cur_stream());
+  if (with_f16) return {y, h, y16};
   return {y, h};
+}
+
+// Absorbed-MLA decode prep (T == 1), one launch: RMS-normalise c_kv, rope
+// k_pe, store the [c_kv | k_pe] row into the compressed cache at the
+// position, rope every head's q_pe, and lay q_nope out head-major for
+// the W_UK bmm.
+//   qh [B, 1, nh, nope+rope] and ckv [B, 1, rank+rope]: contiguous or
+//   split views of a wider buffer;  cache [B, 1, Scap, rank+rope]
+// Returns (q_pe [B, nh, rope], q_nope [nh, B, nope]).
+std::vector<torch::Tensor> mla_decode_prep(
+    torch::Tensor qh, torch::Tensor ckv, torch::Tensor w, double eps,
+    double w_off, torch::Tensor cos, torch::Tensor sin, torch::Tensor cache,
+    int64_t rope, c10::optional<torch::Tensor> pos, int64_t pos0) {
+  check_bf16(qh, "qh");
+  check_bf16(ckv, "ckv");
+  check_bf16(w, "w");
+  check_bf16(cache, "cache");
+  TORCH_CHECK(qh.dim() == 4 && qh.size(1) == 1, "qh must be [B, 1, nh, D]");
+  TORCH_CHECK(ckv.dim() == 3 && ckv.size(1) == 1 && ckv.size(0) == qh.size(0),
+              "ckv must be [B, 1, rank+rope]");
+  const int B = qh.size(0), nh = qh.size(2);
+  const int nope = qh.size(3) - rope;
+  const int rank = ckv.size(2) - rope;
+  TORCH_CHECK(rope >= 2 && rope % 2 == 0 && nope >= 8 && nope % 8 == 0 &&
+                  rank >= 4 && rank % 4 == 0,
+              "mla_decode_prep needs rope % 2 == 0, nope % 8 == 0, "
+              "rank % 4 == 0 (got rope=", rope, ", nope=", nope, ", rank=",
+              rank, ")");
+  TORCH_CHECK(w.numel() == rank, "norm weight must hold rank elements");
+  TORCH_CHECK(cache.dim() == 4 && cache.is_contiguous() &&
+                  cache.size(0) == B && cache.size(1) == 1 &&
+                  cache.size(3) == rank + rope,
+              "cache must be contiguous [B, 1, Scap, rank+rope]");
+  const long Scap = cache.size(2);
+  auto cc = cos.contiguous();
+  auto sc = sin.contiguous();
+  const long csb = rope_table_bstride(cc, sc, B, 1, rope / 2);
+  int pbs;
+  const int* pp = pos_arg(pos, B, pbs);
+  if (!pp)
+    TORCH_CHECK(pos0 >= 0 && pos0 < Scap, "position ", pos0,
+                " outside the cache capacity ", Scap);
+  // split views read in place when rows keep the vector alignment the
+  // kernel loads with (16 B for q_nope, 8 B for c_kv)
+  torch::Tensor qv = qh, cv = ckv;
+  if (!(qh.stride(3) == 1 && qh.stride(1) % 8 == 0 && qh.stride(2) % 8 == 0 &&
+        (B == 1 || qh.stride(0) % 8 == 0) &&
+        ((uintptr_t)qh.data_ptr()) % 16 == 0))
+    qv = qh.contiguous();
+  if (!(ckv.stride(2) == 1 && (B == 1 || ckv.stride(0) % 4 == 0) &&
+        ((uintptr_t)ckv.data_ptr()) % 8 == 0))
+    cv = ckv.contiguous();
+  auto q_pe = torch::empty({B, nh, rope}, qh.options());
+  auto q_nope = torch::empty({nh, B, nope}, qh.options());
+  launch_mla_decode_prep(qv.data_ptr(), cv.data_ptr(),
+                         w.contiguous().data_ptr(), cc.data_ptr<float>(),
+                         sc.data_ptr<float>(), cache.data_ptr(),
+                         q_pe.data_ptr(), q_nope.data_ptr(), pp, pbs,
+                         (int)pos0, B, nh, nope, (int)rope, rank, Scap,
+                         qv.stride(0), qv.stride(2), cv.stride(0), csb,
+                         (float)eps, (float)w_off, cur_stream());
+  return {q_pe, q_nope};
+}
+
+// out = h + (bf16(acc) + shared), each step rounded to bf16 as the
+// unfused acc.to(bf16) / y + shared / h + mlp sequence rounds it
+torch::Tensor moe_finalize(torch::Tensor acc, c10::optional<torch::Tensor> shared,
+                           torch::Tensor h) {
+  check_bf16(h, "h");
+  TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == torch::kFloat32 &&
+                  acc.is_contiguous(), "acc must be contiguous fp32 on GPU");
+  TORCH_CHECK(h.numel() == acc.numel(), "h/acc size mismatch");
+  auto hc = h.contiguous();
+  torch::Tensor sc;
+  if (shared.has_value()) {
+    check_bf16(*shared, "shared");
+    TORCH_CHECK(shared->numel() == acc.numel(), "shared/acc size mismatch");
+    sc = shared->contiguous();
+  }
+  auto out = torch::empty(h.sizes(), hc.options());
+  launch_moe_finalize(acc.data_ptr<float>(),
+                      sc.defined() ? sc.data_ptr() : nullptr, hc.data_ptr(),
+                      out.data_ptr(), acc.numel(), cur_stream());
+  return out;
 }
 
 torch::Tensor glu(torch::Tensor gate, torch::Tensor up, bool gelu) {
@@ -327,16 +425,20 @@ void mla_append_kv(torch::Tensor kvh, torch::Tensor kpe, torch::Tensor kcache,
                        cur_stream());
 }
 
-// q [B, Hq, 1, Dk]; k/v: cache views [B, Hkv, S, D] with row-contiguous
-// last dim over a [B, Hkv, Scap, D] buffer.
-torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                          double scale, double softcap, int64_t window,
-                          c10::optional<torch::Tensor> pos) {
-  check_bf16(q, "q");
+// Shared body of attn_decode / attn_decode_split.
+// qn: [B, Hq, Dk - Dr] view (any batch/head strides, unit last stride);
+// qr: [B, Hq, Dr] view or undefined (Dr = 0).  head_major lays the
+// output out as [Hq, B, Dv] (the W_UV bmm operand) instead of
+// [B, Hq, 1, Dv].
+torch::Tensor attn_decode_impl(const torch::Tensor& qn, const torch::Tensor& qr,
+                               torch::Tensor k, torch::Tensor v, double scale,
+                               double softcap, int64_t window,
+                               c10::optional<torch::Tensor> pos,
+                               bool head_major) {
   check_bf16(k, "k");
-  TORCH_CHECK(q.size(2) == 1, "attn_decode needs Tq == 1");
-  auto qc = q.contiguous();
-  const int B = qc.size(0), Hq = qc.size(1), Dk = qc.size(3);
+  const torch::Tensor& qc = qn;
+  const int Dr = qr.defined() ? (int)qr.size(2) : 0;
+  const int B = qn.size(0), Hq = qn.size(1), Dk = qn.size(2) + Dr;
   const int Hkv = k.size(1), S = k.size(2);
   const int Dv = v.size(3);
   TORCH_CHECK(k.stride(3) == 1 && v.stride(3) == 1, "K/V rows must be contiguous");
@@ -352,7 +454,10 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   long kScap = k.stride(1) / Dk;
   long vScap = v.stride(1) / vstride;
   TORCH_CHECK(kScap == vScap, "K/V capacity mismatch");
-  auto out = torch::empty({B, Hq, 1, Dv}, qc.options());
+  auto out = head_major ? torch::empty({Hq, B, Dv}, qc.options())
+                        : torch::empty({B, Hq, 1, Dv}, qc.options());
+  const long o_bs = head_major ? Dv : (long)Hq * Dv;
+  const long o_hs = head_major ? (long)B * Dv : Dv;
   int sbs;
   const int* s_ptr = pos_arg(pos, B, sbs);
   // split-S for parallelism: target ~1024 blocks, slices of >= 512 keys
@@ -373,11 +478,45 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
     part_o = po.data_ptr<float>();
     part_ml = pml.data_ptr<float>();
   }
-  launch_attn_decode(qc.data_ptr(), k.data_ptr(), v.data_ptr(),
-                     out.data_ptr(), part_o, part_ml, nsplit, s_ptr, sbs, B,
-                     Hq, Hkv, S, kScap, Dk, Dv, vstride, (float)scale,
-                     (float)softcap, (int)window, cur_stream());
+  launch_attn_decode(qn.data_ptr(), Dr ? qr.data_ptr() : nullptr,
+                     k.data_ptr(), v.data_ptr(), out.data_ptr(), part_o,
+                     part_ml, nsplit, s_ptr, sbs, B, Hq, Hkv, S, kScap, Dk,
+                     Dv, vstride, (float)scale, (float)softcap, (int)window,
+                     Dr, qn.stride(0), qn.stride(1), Dr ? qr.stride(0) : 0,
+                     Dr ? qr.stride(1) : 0, o_bs, o_hs, cur_stream());
   return out;
+}
+
+// q [B, Hq, 1, Dk]; k/v: cache views [B, Hkv, S, D] with row-contiguous
+// last dim over a [B, Hkv, Scap, D] buffer.
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                          double scale, double softcap, int64_t window,
+                          c10::optional<torch::Tensor> pos) {
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "attn_decode needs Tq == 1");
+  auto qc = q.contiguous();
+  return attn_decode_impl(qc.view({qc.size(0), qc.size(1), qc.size(3)}),
+                          torch::Tensor(), k, v, scale, softcap, window, pos,
+                          false);
+}
+
+// Two-source q (absorbed MLA): q_nope [B, Hq, Dk - Dr] and q_rope
+// [B, Hq, Dr], both read in place through their (batch, head) strides;
+// returns [Hq, B, Dv].
+torch::Tensor attn_decode_split(torch::Tensor q_nope, torch::Tensor q_rope,
+                                torch::Tensor k, torch::Tensor v, double scale,
+                                double softcap, int64_t window,
+                                c10::optional<torch::Tensor> pos) {
+  check_bf16(q_nope, "q_nope");
+  check_bf16(q_rope, "q_rope");
+  TORCH_CHECK(q_nope.dim() == 3 && q_rope.dim() == 3 &&
+                  q_nope.size(0) == q_rope.size(0) &&
+                  q_nope.size(1) == q_rope.size(1) && q_rope.size(2) > 0,
+              "q_nope/q_rope must be [B, Hq, *] with matching B, Hq");
+  TORCH_CHECK(q_nope.stride(2) == 1 && q_rope.stride(2) == 1,
+              "q rows must be contiguous");
+  return attn_decode_impl(q_nope, q_rope, k, v, scale, softcap, window, pos,
+                          true);
 }
 
 // q [B, Hq, T, Dk]; k/v cache views [B, Hkv, S, D] (row-contiguous)
@@ -614,13 +753,16 @@ torch::Tensor moe_w4_mfma(torch::Tensor x, torch::Tensor wq,
 
 // Fused fp16-dequant gate+up+SiLU over repacked quant words.
 // x [N, H] fp16; gq/uq [E, I, H*bits/32] repacked; scales/biases bf16.
-torch::Tensor moe_w4f16_gateup(torch::Tensor x, torch::Tensor gq,
-                               torch::Tensor uq, torch::Tensor gsc,
-                               torch::Tensor gbi, torch::Tensor usc,
-                               torch::Tensor ubi, torch::Tensor sub_expert,
-                               torch::Tensor sub_off, torch::Tensor sub_cnt,
-                               torch::Tensor sorted_tok, int64_t P,
-                               int64_t gs, int64_t bits) {
+// clear: optional fp32 buffer the launch zeroes (the down kernel's
+// accumulator).
+torch::Tensor moe_w4f16_gateup_impl(torch::Tensor x, torch::Tensor gq,
+                                    torch::Tensor uq, torch::Tensor gsc,
+                                    torch::Tensor gbi, torch::Tensor usc,
+                                    torch::Tensor ubi, torch::Tensor sub_expert,
+                                    torch::Tensor sub_off, torch::Tensor sub_cnt,
+                                    torch::Tensor sorted_tok, int64_t P,
+                                    int64_t gs, int64_t bits,
+                                    const torch::Tensor& clear) {
   TORCH_CHECK(x.scalar_type() == torch::kHalf, "x must be fp16");
   const int H = x.size(1);
   const int I = gq.size(1);
@@ -633,23 +775,66 @@ torch::Tensor moe_w4f16_gateup(torch::Tensor x, torch::Tensor gq,
       gbi.data_ptr(), usc.data_ptr(), ubi.data_ptr(), h.data_ptr(),
       sub_expert.data_ptr<int>(), sub_off.data_ptr<int>(),
       sub_cnt.data_ptr<int>(), sorted_tok.data_ptr<int>(), S, H, I, (int)gs,
-      (int)bits, cur_stream());
+      (int)bits, clear.defined() ? clear.data_ptr<float>() : nullptr,
+      clear.defined() ? clear.numel() : 0, cur_stream());
   return h;
 }
 
+torch::Tensor moe_w4f16_gateup(torch::Tensor x, torch::Tensor gq,
+                               torch::Tensor uq, torch::Tensor gsc,
+                               torch::Tensor gbi, torch::Tensor usc,
+                               torch::Tensor ubi, torch::Tensor sub_expert,
+                               torch::Tensor sub_off, torch::Tensor sub_cnt,
+                               torch::Tensor sorted_tok, int64_t P,
+                               int64_t gs, int64_t bits) {
+  return moe_w4f16_gateup_impl(x, gq, uq, gsc, gbi, usc, ubi, sub_expert,
+                               sub_off, sub_cnt, sorted_tok, P, gs, bits,
+                               torch::Tensor());
+}
+
+// gate+up that also hands moe_w4f16_down its accumulator: fp32 [N, Hout],
+// allocated uninitialised here and zeroed by the gate+up launch itself
+// (no separate fill launch, nothing kept between calls).
+// Returns (h, acc).
+std::vector<torch::Tensor> moe_w4f16_gateup_acc(
+    torch::Tensor x, torch::Tensor gq, torch::Tensor uq, torch::Tensor gsc,
+    torch::Tensor gbi, torch::Tensor usc, torch::Tensor ubi,
+    torch::Tensor sub_expert, torch::Tensor sub_off, torch::Tensor sub_cnt,
+    torch::Tensor sorted_tok, int64_t P, int64_t gs, int64_t bits, int64_t N,
+    int64_t Hout) {
+  TORCH_CHECK(N >= 1 && Hout >= 1, "accumulator shape must be positive");
+  auto acc = torch::empty({N, Hout}, x.options().dtype(torch::kFloat32));
+  auto h = moe_w4f16_gateup_impl(x, gq, uq, gsc, gbi, usc, ubi, sub_expert,
+                                 sub_off, sub_cnt, sorted_tok, P, gs, bits,
+                                 acc);
+  return {h, acc};
+}
+
+// acc: the fp32 [N, H] accumulator that a preceding moe_w4f16_gateup_acc
+// launch zeroed on this stream; without it the binding zero-fills its
+// own.
 torch::Tensor moe_w4f16_down(torch::Tensor hh, torch::Tensor dq,
                              torch::Tensor dsc, torch::Tensor dbi,
                              torch::Tensor sub_expert, torch::Tensor sub_off,
                              torch::Tensor sub_cnt, torch::Tensor sorted_tok,
                              torch::Tensor sorted_wt, int64_t N, int64_t gs,
-                             int64_t bits) {
+                             int64_t bits, c10::optional<torch::Tensor> acc) {
   TORCH_CHECK(hh.scalar_type() == torch::kHalf, "h must be fp16");
   const int I = hh.size(1);
   const int H = dq.size(1);
   const int S = sub_expert.size(0);
   TORCH_CHECK(I % 32 == 0, "I%32 required");
   TORCH_CHECK(gs == 32 || gs == 64 || gs == 128, "gs must be 32/64/128");
-  auto out = torch::zeros({N, H}, hh.options().dtype(torch::kFloat32));
+  torch::Tensor out;
+  if (acc.has_value()) {
+    out = *acc;
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kFloat32 &&
+                    out.is_contiguous() && out.dim() == 2 &&
+                    out.size(0) == N && out.size(1) == H,
+                "acc must be contiguous fp32 [N, H]");
+  } else {
+    out = torch::zeros({N, H}, hh.options().dtype(torch::kFloat32));
+  }
   launch_moe_w4f16_down(
       hh.contiguous().data_ptr(), dq.data_ptr(), dsc.data_ptr(),
       dbi.data_ptr(), out.data_ptr<float>(), sub_expert.data_ptr<int>(),
@@ -727,7 +912,16 @@ std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rms_norm", &rms_norm, "fused RMSNorm (gfx950)");
-  m.def("rms_norm_residual", &rms_norm_residual);
+  m.def("rms_norm_residual", &rms_norm_residual, pybind11::arg("x"),
+        pybind11::arg("resid"), pybind11::arg("w"), pybind11::arg("eps"),
+        pybind11::arg("w_off"), pybind11::arg("with_f16") = false);
+  m.def("mla_decode_prep", &mla_decode_prep, pybind11::arg("qh"),
+        pybind11::arg("ckv"), pybind11::arg("w"), pybind11::arg("eps"),
+        pybind11::arg("w_off"), pybind11::arg("cos"), pybind11::arg("sin"),
+        pybind11::arg("cache"), pybind11::arg("rope"),
+        pybind11::arg("pos") = pybind11::none(), pybind11::arg("pos0") = 0);
+  m.def("moe_finalize", &moe_finalize, pybind11::arg("acc"),
+        pybind11::arg("shared"), pybind11::arg("h"));
   m.def("glu", &glu);
   m.def("softcap", &softcap_op);
   m.def("apply_rope", &apply_rope);
@@ -742,6 +936,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("pos0") = 0);
   m.def("attn_decode", &attn_decode, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("softcap"),
+        pybind11::arg("window"), pybind11::arg("pos") = pybind11::none());
+  m.def("attn_decode_split", &attn_decode_split, pybind11::arg("q_nope"),
+        pybind11::arg("q_rope"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("scale"), pybind11::arg("softcap"),
         pybind11::arg("window"), pybind11::arg("pos") = pybind11::none());
   m.def("attn_decode_shape_ok", [](int64_t g, int64_t dv) {
     return attn_decode_supported_shape((int)g, (int)dv);
@@ -770,7 +968,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_down_grouped", &moe_down_grouped);
   m.def("moe_w4_mfma", &moe_w4_mfma);
   m.def("moe_w4f16_gateup", &moe_w4f16_gateup);
-  m.def("moe_w4f16_down", &moe_w4f16_down);
+  m.def("moe_w4f16_gateup_acc", &moe_w4f16_gateup_acc);
+  m.def("moe_w4f16_down", &moe_w4f16_down, pybind11::arg("hh"),
+        pybind11::arg("dq"), pybind11::arg("dsc"), pybind11::arg("dbi"),
+        pybind11::arg("sub_expert"), pybind11::arg("sub_off"),
+        pybind11::arg("sub_cnt"), pybind11::arg("sorted_tok"),
+        pybind11::arg("sorted_wt"), pybind11::arg("N"), pybind11::arg("gs"),
+        pybind11::arg("bits"), pybind11::arg("acc") = pybind11::none());
   m.def("moe_gate_subranges", &moe_gate_subranges, pybind11::arg("logits"),
         pybind11::arg("top_k"), pybind11::arg("s_upper"),
         pybind11::arg("max_tok"), pybind11::arg("routed_scaling"),

@@ -9,13 +9,16 @@
 // Optional fused residual: h = x + r; y = norm(h); h written back.
 // ---------------------------------------------------------------------------
 
+typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
+
 template <int BLOCK, bool RESIDUAL>
 __global__ void rms_norm_kernel(const short* __restrict__ x,
                                 const short* __restrict__ resid,
                                 short* __restrict__ y,
                                 short* __restrict__ h_out,
                                 const short* __restrict__ w, int H, float eps,
-                                float w_off, long xstride) {
+                                float w_off, long xstride,
+                                _Float16* __restrict__ y16) {
   __shared__ float scratch[BLOCK / WAVE];
   const long row = blockIdx.x;
   const short* xr = x + row * xstride;  // strided: x may be a fused-split view
@@ -63,6 +66,13 @@ __global__ void rms_norm_kernel(const short* __restrict__ x,
     o.z = (short)__bfloat16_as_ushort(f2bf(bfbits2f(v.z) * inv * (bfbits2f(wvv.z) + w_off)));
     o.w = (short)__bfloat16_as_ushort(f2bf(bfbits2f(v.w) * inv * (bfbits2f(wvv.w) + w_off)));
     reinterpret_cast<short4v*>(yr)[i] = o;
+    if (y16) {
+      // optional fp16 copy of the bf16-ROUNDED y (what y.to(float16)
+      // gives): saves the packed MoE kernels' separate cast launch
+      f16x4v o16 = {(_Float16)bfbits2f(o.x), (_Float16)bfbits2f(o.y),
+                    (_Float16)bfbits2f(o.z), (_Float16)bfbits2f(o.w)};
+      reinterpret_cast<f16x4v*>(y16 + row * H)[i] = o16;
+    }
   }
 }
 
@@ -72,17 +82,18 @@ extern "C" void launch_rms_norm(const void* x, void* y, const void* w,
   constexpr int BLOCK = 256;
   rms_norm_kernel<BLOCK, false><<<dim3((unsigned)rows), dim3(BLOCK), 0, stream>>>(
       (const short*)x, nullptr, (short*)y, nullptr, (const short*)w, H, eps,
-      w_off, xstride);
+      w_off, xstride, nullptr);
 }
 
 extern "C" void launch_rms_norm_residual(const void* x, const void* resid,
                                          void* y, void* h_out, const void* w,
                                          long rows, int H, float eps,
-                                         float w_off, hipStream_t stream) {
+                                         float w_off, void* y16,
+                                         hipStream_t stream) {
   constexpr int BLOCK = 256;
   rms_norm_kernel<BLOCK, true><<<dim3((unsigned)rows), dim3(BLOCK), 0, stream>>>(
       (const short*)x, (const short*)resid, (short*)y, (short*)h_out,
-      (const short*)w, H, eps, w_off, H);
+      (const short*)w, H, eps, w_off, H, (_Float16*)y16);
 }
 
 // ---------------------------------------------------------------------------
@@ -387,4 +398,186 @@ extern "C" void launch_mla_append_kv(const void* kvh, const void* kpe,
                                    pos_bstride, pos0, B, T, nh, nope, vd,
                                    rope, Scap,
                                    kpe_rstride);
+}
+
+// ---------------------------------------------------------------------------
+// MLA decode prep (T == 1): one launch for what the absorbed decode path
+// ran as rope(q_pe) + rms_norm(c_kv) + rope(k_pe) + mla_append_kv (+ the
+// strided-view copy in front of the W_UK bmm).
+//   qh   [B, nh, nope+rope] view (row stride q_rs, head stride q_hs)
+//   ckv  [B, rank+rope] view (row stride ckv_rs)
+//   cache [B, 1, Scap, rank+rope]; row b lands at its position
+//   q_pe_out [B, nh, rope]; q_nope_out [nh, B, nope] (bmm operand layout)
+// grid = (B, 1 + ceil(nh*rope/2 / 256) + ceil(nh*nope/8 / 256)):
+//   y == 0      : the c_kv row — same block_sum and rounding points as
+//                 rms_norm_kernel<256, false> — plus rope(k_pe), stored
+//                 straight into the cache row
+//   next blocks : one thread per (head, rope pair) of q_pe
+//   last blocks : 16-byte copies of q_nope into head-major layout
+// ---------------------------------------------------------------------------
+
+#define PREP_BLOCK 256
+
+// One interleaved rope pair, bit-identical to rope_kernel.  The source
+// expressions x1*c - x2*s and x2*c + x1*s leave the compiler free to fuse
+// either product into the fma; the choices differ in the last fp32 bit
+// and move about one bf16 result in 1e5.  This pins the forms rope_kernel
+// is compiled to (checked against it on 4M pairs on the GPU, and by
+// test_mla_decode_prep_rounding_many_draws): the s-products are rounded
+// on their own, the c-products are fused.
+__device__ __forceinline__ void rope_pair_pinned(float x1, float x2, float c,
+                                                 float s, float& o1,
+                                                 float& o2) {
+#pragma clang fp contract(off)
+  const float x2s = x2 * s;
+  const float x1s = x1 * s;
+  o1 = __builtin_fmaf(x1, c, -x2s);
+  o2 = __builtin_fmaf(x2, c, x1s);
+}
+
+__global__ __launch_bounds__(PREP_BLOCK) void mla_decode_prep_kernel(
+    const short* __restrict__ qh, const short* __restrict__ ckv,
+    const short* __restrict__ w, const float* __restrict__ cost,
+    const float* __restrict__ sint, short* __restrict__ cache,
+    short* __restrict__ q_pe_out, short* __restrict__ q_nope_out,
+    const int* __restrict__ pos_ptr, int pos_bstride, int pos0, int B, int nh,
+    int nope, int rope, int rank, long Scap, long q_rs, long q_hs, long ckv_rs,
+    long cs_bstride, float eps, float w_off, int n_pe_blocks) {
+  __shared__ float scratch[PREP_BLOCK / WAVE];
+  const int b = blockIdx.x;
+  const int half = rope / 2;
+  const float* c = cost + (long)b * cs_bstride;
+  const float* s = sint + (long)b * cs_bstride;
+
+  if (blockIdx.y == 0) {
+    const long pos = pos_ptr ? pos_ptr[b * pos_bstride] : pos0;
+    const short* xr = ckv + (long)b * ckv_rs;
+    float ss = 0.0f;
+    const int nvec = rank / 4;
+    const short4v* xv = reinterpret_cast<const short4v*>(xr);
+    for (int i = threadIdx.x; i < nvec; i += PREP_BLOCK) {
+      short4v v = xv[i];
+      float f0 = bfbits2f(v.x), f1 = bfbits2f(v.y), f2 = bfbits2f(v.z),
+            f3 = bfbits2f(v.w);
+      {
+        // as rms_norm_kernel compiles it: four rounded squares, no fma
+#pragma clang fp contract(off)
+        ss += f0 * f0 + f1 * f1 + f2 * f2 + f3 * f3;
+      }
+    }
+    ss = block_sum<PREP_BLOCK>(ss, scratch);
+    // a position outside the cache would write out of bounds
+    if (pos < 0 || pos >= Scap) return;
+    const float inv = rsqrtf(ss / (float)rank + eps);
+    short* krow = cache + ((long)b * Scap + pos) * (rank + rope);
+    const short4v* wv = reinterpret_cast<const short4v*>(w);
+    for (int i = threadIdx.x; i < nvec; i += PREP_BLOCK) {
+      short4v v = xv[i];
+      short4v wvv = wv[i];
+      short4v o;
+      o.x = (short)__bfloat16_as_ushort(f2bf(bfbits2f(v.x) * inv * (bfbits2f(wvv.x) + w_off)));
+      o.y = (short)__bfloat16_as_ushort(f2bf(bfbits2f(v.y) * inv * (bfbits2f(wvv.y) + w_off)));
+      o.z = (short)__bfloat16_as_ushort(f2bf(bfbits2f(v.z) * inv * (bfbits2f(wvv.z) + w_off)));
+      o.w = (short)__bfloat16_as_ushort(f2bf(bfbits2f(v.w) * inv * (bfbits2f(wvv.w) + w_off)));
+      reinterpret_cast<short4v*>(krow)[i] = o;
+    }
+    const short* pe = xr + rank;
+    for (int p = threadIdx.x; p < half; p += PREP_BLOCK) {
+      const float x1 = bfbits2f(pe[2 * p]), x2 = bfbits2f(pe[2 * p + 1]);
+      float o1, o2;
+      rope_pair_pinned(x1, x2, c[p], s[p], o1, o2);
+      krow[rank + 2 * p] = (short)__bfloat16_as_ushort(f2bf(o1));
+      krow[rank + 2 * p + 1] = (short)__bfloat16_as_ushort(f2bf(o2));
+    }
+    return;
+  }
+
+  const short* qrow = qh + (long)b * q_rs;
+  if ((int)blockIdx.y <= n_pe_blocks) {
+    const int idx = (blockIdx.y - 1) * PREP_BLOCK + threadIdx.x;
+    if (idx >= nh * half) return;
+    const int head = idx / half, p = idx - head * half;
+    const short* xr = qrow + (long)head * q_hs + nope;
+    short* yr = q_pe_out + ((long)b * nh + head) * rope;
+    const float x1 = bfbits2f(xr[2 * p]), x2 = bfbits2f(xr[2 * p + 1]);
+    float o1, o2;
+    rope_pair_pinned(x1, x2, c[p], s[p], o1, o2);
+    yr[2 * p] = (short)__bfloat16_as_ushort(f2bf(o1));
+    yr[2 * p + 1] = (short)__bfloat16_as_ushort(f2bf(o2));
+    return;
+  }
+
+  const int nv8 = nope / 8;
+  const int idx = (blockIdx.y - 1 - n_pe_blocks) * PREP_BLOCK + threadIdx.x;
+  if (idx >= nh * nv8) return;
+  const int head = idx / nv8, v = idx - head * nv8;
+  reinterpret_cast<short8v*>(q_nope_out + ((long)head * B + b) * nope)[v] =
+      *reinterpret_cast<const short8v*>(qrow + (long)head * q_hs + v * 8);
+}
+
+extern "C" void launch_mla_decode_prep(
+    const void* qh, const void* ckv, const void* w, const float* cost,
+    const float* sint, void* cache, void* q_pe_out, void* q_nope_out,
+    const int* pos_ptr, int pos_bstride, int pos0, int B, int nh, int nope,
+    int rope, int rank, long Scap, long q_rs, long q_hs, long ckv_rs,
+    long cs_bstride, float eps, float w_off, hipStream_t stream) {
+  const int n_pe = (nh * (rope / 2) + PREP_BLOCK - 1) / PREP_BLOCK;
+  const int n_cp = (nh * (nope / 8) + PREP_BLOCK - 1) / PREP_BLOCK;
+  mla_decode_prep_kernel<<<dim3((unsigned)B, (unsigned)(1 + n_pe + n_cp)),
+                           dim3(PREP_BLOCK), 0, stream>>>(
+      (const short*)qh, (const short*)ckv, (const short*)w, cost, sint,
+      (short*)cache, (short*)q_pe_out, (short*)q_nope_out, pos_ptr,
+      pos_bstride, pos0, B, nh, nope, rope, rank, Scap, q_rs, q_hs, ckv_rs,
+      cs_bstride, eps, w_off, n_pe);
+}
+
+// ---------------------------------------------------------------------------
+// MoE finalize: out = h + (bf16(acc) + shared) in one pass, with a bf16
+// rounding at each of the three points where the unfused sequence
+// (acc.to(bf16), y + shared, h + mlp) rounds, so the result is
+// bit-identical.  acc fp32 [n]; shared (optional) / h / out bf16 [n].
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ short bf_round_bits(float v) {
+  return (short)__bfloat16_as_ushort(f2bf(v));
+}
+
+__global__ void moe_finalize_kernel(const float* __restrict__ acc,
+                                    const short* __restrict__ shared,
+                                    const short* __restrict__ h,
+                                    short* __restrict__ out, long n) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long n4 = n / 4;
+  for (long i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4v a = reinterpret_cast<const float4v*>(acc)[i];
+    const short4v hv = reinterpret_cast<const short4v*>(h)[i];
+    short4v sv = {0, 0, 0, 0};
+    if (shared) sv = reinterpret_cast<const short4v*>(shared)[i];
+    short4v o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      short y = bf_round_bits(a[k]);
+      if (shared) y = bf_round_bits(bfbits2f(y) + bfbits2f(sv[k]));
+      o[k] = bf_round_bits(bfbits2f(hv[k]) + bfbits2f(y));
+    }
+    reinterpret_cast<short4v*>(out)[i] = o;
+  }
+  // n % 4 tail
+  for (long i = n4 * 4 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    short y = bf_round_bits(acc[i]);
+    if (shared) y = bf_round_bits(bfbits2f(y) + bfbits2f(shared[i]));
+    out[i] = bf_round_bits(bfbits2f(h[i]) + bfbits2f(y));
+  }
+}
+
+extern "C" void launch_moe_finalize(const float* acc, const void* shared,
+                                    const void* h, void* out, long n,
+                                    hipStream_t stream) {
+  const int block = 256;
+  long want = (n / 4 + block - 1) / block;
+  int grid = (int)min(want, (long)(256 * 8));
+  if (grid < 1) grid = 1;
+  moe_finalize_kernel<<<dim3(grid), dim3(block), 0, stream>>>(
+      acc, (const short*)shared, (const short*)h, (short*)out, n);
 }

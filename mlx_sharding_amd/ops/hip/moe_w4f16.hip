@@ -91,6 +91,11 @@ static_assert(WF_NSL == 8, "batch_kk remap requires 8-slice batches");
 //   gs_/gb_/us_/ub_: [E, I, H/gs] bf16 scales/biases (original layout)
 //   h:  [P, I] fp16 out
 // grid = (ceil(I/64), S); LDS-free like the bf16 MFMA pair.
+//   clear: optional fp32 [clear_n] buffer zeroed by this launch — the
+//   down kernel's atomic accumulator, which follows on the same stream
+//   (replaces a separate fill launch).  Every block clears a grid-stride
+//   share BEFORE any early exit, so the whole buffer is covered whatever
+//   the grid size and however many sub-range slots are padding.
 // ---------------------------------------------------------------------------
 template <int BITS, int GS>
 __global__ __launch_bounds__(WF_BLOCK) void moe_w4f16_gateup_kernel(
@@ -100,7 +105,16 @@ __global__ __launch_bounds__(WF_BLOCK) void moe_w4f16_gateup_kernel(
     const short* __restrict__ ubi, _Float16* __restrict__ h,
     const int* __restrict__ sub_expert, const int* __restrict__ sub_off,
     const int* __restrict__ sub_cnt, const int* __restrict__ sorted_tok,
-    int H, int I) {
+    int H, int I, float* __restrict__ clear, long clear_n) {
+  if (clear) {
+    const long nthr = (long)gridDim.x * gridDim.y * WF_BLOCK;
+    const long t0 =
+        ((long)blockIdx.y * gridDim.x + blockIdx.x) * WF_BLOCK + threadIdx.x;
+    const long n4 = clear_n / 4;  // allocation is 16-byte aligned
+    for (long i = t0; i < n4; i += nthr)
+      reinterpret_cast<float4v*>(clear)[i] = float4v{0, 0, 0, 0};
+    for (long i = n4 * 4 + t0; i < clear_n; i += nthr) clear[i] = 0.0f;
+  }
   const int s = blockIdx.y;
   const int e = sub_expert[s];
   const int p0 = sub_off[s];
@@ -496,14 +510,15 @@ static void dispatch_gateup(const void* x, const void* gq, const void* uq,
                             const void* gsc, const void* gbi, const void* usc,
                             const void* ubi, void* h, const int* se,
                             const int* so, const int* sc, const int* st,
-                            int S, int H, int I, int gs, hipStream_t stream) {
+                            int S, int H, int I, int gs, float* clear,
+                            long clear_n, hipStream_t stream) {
   const int gx = (I + WF_WAVES * 16 - 1) / (WF_WAVES * 16);
   dim3 grid(gx, S), block(WF_BLOCK);
 #define GU_CASE(GSV)                                                        \
   moe_w4f16_gateup_kernel<BITS, GSV><<<grid, block, 0, stream>>>(           \
       (const _Float16*)x, (const unsigned int*)gq, (const unsigned int*)uq, \
       (const short*)gsc, (const short*)gbi, (const short*)usc,              \
-      (const short*)ubi, (_Float16*)h, se, so, sc, st, H, I)
+      (const short*)ubi, (_Float16*)h, se, so, sc, st, H, I, clear, clear_n)
   if (gs == 32) GU_CASE(32);
   else if (gs == 64) GU_CASE(64);
   else GU_CASE(128);
@@ -515,13 +530,15 @@ extern "C" void launch_moe_w4f16_gateup(
     const void* gbi, const void* usc, const void* ubi, void* h,
     const int* sub_expert, const int* sub_off, const int* sub_cnt,
     const int* sorted_tok, int S, int H, int I, int gs, int bits,
-    hipStream_t stream) {
+    float* clear, long clear_n, hipStream_t stream) {
   if (bits == 4)
     dispatch_gateup<4>(x, gq, uq, gsc, gbi, usc, ubi, h, sub_expert, sub_off,
-                       sub_cnt, sorted_tok, S, H, I, gs, stream);
+                       sub_cnt, sorted_tok, S, H, I, gs, clear, clear_n,
+                       stream);
   else
     dispatch_gateup<8>(x, gq, uq, gsc, gbi, usc, ubi, h, sub_expert, sub_off,
-                       sub_cnt, sorted_tok, S, H, I, gs, stream);
+                       sub_cnt, sorted_tok, S, H, I, gs, clear, clear_n,
+                       stream);
 }
 
 template <int BITS>

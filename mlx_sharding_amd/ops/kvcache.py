@@ -105,6 +105,28 @@ class KVCache:
         self.offset += T
         return (self._k[:, :, : self.offset], self._v[:, :, : self.offset])
 
+    def mla_decode_prep(self, qh: torch.Tensor, ckv: torch.Tensor, norm_w,
+                        eps: float, w_off: float, cos, sin, rope: int):
+        """Fused T == 1 absorbed-MLA step on the compressed cache: the
+        [rms_norm(c_kv) | rope(k_pe)] row of ckv [B, 1, rank+rope] goes
+        straight into the cache at the position, and every head of qh
+        [B, 1, nh, nope+rope] is split into roped q_pe [B, nh, rope] and
+        head-major q_nope [nh, B, nope] — one launch.  GPU-only; returns
+        (q_pe, q_nope, k) with k as update() returns it."""
+        from .. import ops as _ops
+        ext = _ops.hip_ext()
+        B = qh.shape[0]
+        if self.graph_pos is not None:
+            q_pe, qn = ext.mla_decode_prep(qh, ckv, norm_w, eps, w_off, cos,
+                                           sin, self._k, rope,
+                                           pos=self.graph_pos)
+            return q_pe, qn, self._k
+        self._ensure(B, self.offset + 1)
+        q_pe, qn = ext.mla_decode_prep(qh, ckv, norm_w, eps, w_off, cos, sin,
+                                       self._k, rope, pos0=self.offset)
+        self.offset += 1
+        return q_pe, qn, self._k[:, :, : self.offset]
+
     def append_rope_kv(self, k: torch.Tensor, v: torch.Tensor,
                        cos: torch.Tensor, sin: torch.Tensor,
                        interleaved: bool = False):
