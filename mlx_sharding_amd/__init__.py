@@ -9,7 +9,7 @@ a wire-compatible gRPC mode is retained for CPU plumbing and the
 control plane).
 
 Layout:
-  models/    sharded model wrappers (llama, gemma2, deepseek_v2)
+  models/    sharded model wrappers (llama, gemma2, deepseek_v2, deepseek_v3)
   ops/       compute ops: torch reference impls + HIP/CDNA4 kernels
   parallel/  transports (gRPC-compat, RCCL) + pipeline engine
   utils/     loading, sampling, detokenizer

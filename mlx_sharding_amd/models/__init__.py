@@ -12,6 +12,7 @@ from .base import StageModel
 from .llama import LlamaStageModel
 from .gemma2 import Gemma2StageModel
 from .deepseek_v2 import DeepseekV2StageModel
+from .deepseek_v3 import DeepseekV3StageModel
 
 MODEL_REMAPPING: Dict[str, str] = {
     "mistral": "llama",
@@ -25,6 +26,7 @@ _REGISTRY: Dict[str, Type[StageModel]] = {
     "llama": LlamaStageModel,
     "gemma2": Gemma2StageModel,
     "deepseek_v2": DeepseekV2StageModel,
+    "deepseek_v3": DeepseekV3StageModel,
 }
 
 

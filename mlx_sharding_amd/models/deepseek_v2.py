@@ -127,6 +127,15 @@ class _StackedLinear(nn.Module):
 
 
 class MLAAttention(nn.Module):
+    # Most heads the compressed-cache (absorbed) decode is taken for.  The
+    # kernel also runs 32/64/128 heads as 8-head groups; only model
+    # families that opted in (DeepSeek-V3) raise this cap — a 128-head V2
+    # stays on the expanded cache until someone has measured the switch.
+    max_absorbed_heads = 16
+    # fuse q_a_proj + kv_a_proj_with_mqa into one GEMM (fuse_model) when
+    # the model has a q_lora_rank
+    fuse_q_lora = False
+
     def __init__(self, cfg: ModelConfig, quant_for, prefix: str):
         super().__init__()
         H = cfg.hidden_size
@@ -178,7 +187,8 @@ class MLAAttention(nn.Module):
         if ext is None:
             return False
         dk = self.kv_lora_rank + self.qk_rope
-        return (dk % 8 == 0 and self.kv_lora_rank % 8 == 0
+        return (self.n_heads <= self.max_absorbed_heads
+                and dk % 8 == 0 and self.kv_lora_rank % 8 == 0
                 and ext.attn_decode_shape_ok(self.n_heads, self.kv_lora_rank))
 
     def _ensure_absorb(self, device, dtype):
@@ -195,6 +205,18 @@ class MLAAttention(nn.Module):
         self._w_uk = w[:, : self.qk_nope, :].contiguous()
         self._w_uv = w[:, self.qk_nope:, :].transpose(1, 2).contiguous()
 
+    def _project_q(self, x):
+        """(q [.., nh*qk_head_dim], kv_a output or None).  The fused GEMM
+        yields q itself without a q_lora_rank, the q_a latent with one."""
+        if self._fused_qkv is not None:
+            qh, ckv = self._fused_qkv(x)
+            if self.q_lora_rank:
+                qh = self.q_b_proj(self.q_a_layernorm(qh))
+            return qh, ckv
+        if self.q_lora_rank:
+            return self.q_b_proj(self.q_a_layernorm(self.q_a_proj(x))), None
+        return self.q_proj(x), None
+
     def forward(self, x, cos, sin, cache: Optional[KVCache]):
         if cache is not None and cache.n_kv_heads == 1 and self.n_heads > 1:
             return self._forward_absorbed(x, cos, sin, cache)
@@ -209,13 +231,7 @@ class MLAAttention(nn.Module):
         absorbed MQA at decode)."""
         B, T, _ = x.shape
         nh, rank, rope = self.n_heads, self.kv_lora_rank, self.qk_rope
-        ckv = None
-        if self._fused_qkv is not None:
-            qh, ckv = self._fused_qkv(x)
-        elif self.q_lora_rank:
-            qh = self.q_b_proj(self.q_a_layernorm(self.q_a_proj(x)))
-        else:
-            qh = self.q_proj(x)
+        qh, ckv = self._project_q(x)
         qh = qh.view(B, T, nh, self.qk_head_dim)
         if (T == 1 and ops.use_native(x) and ops.decode_fuse_enabled()
                 and self.qk_nope % 8 == 0 and rope % 2 == 0):
@@ -308,13 +324,7 @@ class MLAAttention(nn.Module):
 
     def _forward_naive(self, x, cos, sin, cache: Optional[KVCache]):
         B, T, _ = x.shape
-        ckv = None
-        if self._fused_qkv is not None:
-            qh, ckv = self._fused_qkv(x)
-        elif self.q_lora_rank:
-            qh = self.q_b_proj(self.q_a_layernorm(self.q_a_proj(x)))
-        else:
-            qh = self.q_proj(x)
+        qh, ckv = self._project_q(x)
         qh = qh.view(B, T, self.n_heads, self.qk_head_dim)
         q_nope = qh[..., : self.qk_nope]
         q_pe = qh[..., self.qk_nope:]
@@ -389,6 +399,11 @@ class DeepseekV2MoE(nn.Module):
             return self.n_group, self.topk_group
         return 1, 1
 
+    def _gate_kwargs(self) -> dict:
+        """Scoring keywords for ops.moe_gate / ops.moe_gate_subranges
+        (none: the softmax default)."""
+        return {}
+
     def _fused_gate_ok(self, n_tokens: int) -> bool:
         # the limits of ops.moe_gate_subranges; anything else takes the
         # torch gate
@@ -424,7 +439,8 @@ class DeepseekV2MoE(nn.Module):
                                           self.routed_scaling_factor,
                                           self.norm_topk_prob, max_tok=16,
                                           n_group=n_group,
-                                          topk_group=topk_group)
+                                          topk_group=topk_group,
+                                          **self._gate_kwargs())
             acc = self.switch_mlp.forward_subs(flat, subs, 16, raw=True)
             shared = (self.shared_experts(flat)
                       if self.shared_experts is not None else None)
@@ -443,13 +459,15 @@ class DeepseekV2MoE(nn.Module):
                                           self.routed_scaling_factor,
                                           self.norm_topk_prob, max_tok=mt,
                                           n_group=n_group,
-                                          topk_group=topk_group)
+                                          topk_group=topk_group,
+                                          **self._gate_kwargs())
             y = self.switch_mlp.forward_subs(flat, subs, mt)
         else:
             logits = self.gate(flat.to(self.gate.weight.dtype)).float()
-            n_group = self.n_group if self.topk_method == "group_limited_greedy" else 1
-            w, idx = ops.moe_gate(logits, self.top_k, n_group, self.topk_group,
-                                  self.routed_scaling_factor, self.norm_topk_prob)
+            n_group, topk_group = self._gate_groups()
+            w, idx = ops.moe_gate(logits, self.top_k, n_group, topk_group,
+                                  self.routed_scaling_factor, self.norm_topk_prob,
+                                  **self._gate_kwargs())
             w = w.to(x.dtype)
             y = self.switch_mlp(flat, w, idx)
         if self.shared_experts is not None:
@@ -458,16 +476,19 @@ class DeepseekV2MoE(nn.Module):
 
 
 class DeepseekV2DecoderLayer(nn.Module):
+    attn_cls = MLAAttention
+    moe_cls = DeepseekV2MoE
+
     def __init__(self, cfg: ModelConfig, quant_for, prefix: str, layer_idx: int):
         super().__init__()
         eps = cfg.get("rms_norm_eps", 1e-6)
-        self.self_attn = MLAAttention(cfg, quant_for, f"{prefix}.self_attn")
+        self.self_attn = self.attn_cls(cfg, quant_for, f"{prefix}.self_attn")
         first_dense = int(cfg.get("first_k_dense_replace", 0))
         freq = int(cfg.get("moe_layer_freq", 1))
         is_moe = (cfg.get("n_routed_experts") is not None
                   and layer_idx >= first_dense and layer_idx % freq == 0)
         if is_moe:
-            self.mlp = DeepseekV2MoE(cfg, quant_for, f"{prefix}.mlp")
+            self.mlp = self.moe_cls(cfg, quant_for, f"{prefix}.mlp")
         else:
             self.mlp = LlamaMLP(cfg, quant_for, f"{prefix}.mlp")
         self.input_layernorm = RMSNorm(cfg.hidden_size, eps)
@@ -492,6 +513,7 @@ class DeepseekV2DecoderLayer(nn.Module):
 
 class DeepseekV2StageModel(StageModel):
     model_type = "deepseek_v2"
+    layer_cls = DeepseekV2DecoderLayer
 
     def __init__(self, config: ModelConfig, shard: ShardSpec, quant_for=None):
         super().__init__(config, shard)
@@ -503,8 +525,8 @@ class DeepseekV2StageModel(StageModel):
                                                    dtype=torch.bfloat16)
         layers = nn.ModuleDict()
         for i in owned_layer_indices(shard):
-            layers[str(i)] = DeepseekV2DecoderLayer(config, quant_for,
-                                                    f"model.layers.{i}", i)
+            layers[str(i)] = self.layer_cls(config, quant_for,
+                                            f"model.layers.{i}", i)
         self.model.layers = layers
         if shard.is_last:
             self.model.norm = RMSNorm(H, config.get("rms_norm_eps", 1e-6))

@@ -88,6 +88,11 @@ def fuse_model(model) -> int:
             elif isinstance(mod, MLAAttention) and not mod.q_lora_rank:
                 mod._fused_qkv = FusedColumns([mod.q_proj, mod.kv_a_proj_with_mqa])
                 n += 1
+            elif isinstance(mod, MLAAttention) and mod.fuse_q_lora:
+                # q_lora_rank: the q_a latent and kv_a share the input
+                mod._fused_qkv = FusedColumns([mod.q_a_proj,
+                                               mod.kv_a_proj_with_mqa])
+                n += 1
         except AssertionError:
             continue  # mixed quant/bias group — leave unfused
     return n

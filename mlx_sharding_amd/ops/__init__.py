@@ -329,10 +329,12 @@ def quantized_linear(x, w_q, scales, biases, group_size: int, bits: int):
 
 
 def moe_gate(router_logits, top_k: int, n_group: int = 1, topk_group: int = 1,
-             routed_scaling_factor: float = 1.0, norm_topk_prob: bool = False):
+             routed_scaling_factor: float = 1.0, norm_topk_prob: bool = False,
+             *, scoring: str = "softmax", e_bias=None):
     # Router is tiny ([N, E]); fp32 torch path is fine on both devices.
     return ref.moe_gate(router_logits, top_k, n_group, topk_group,
-                        routed_scaling_factor, norm_topk_prob)
+                        routed_scaling_factor, norm_topk_prob,
+                        scoring=scoring, e_bias=e_bias)
 
 
 _MOE_GEMM_MIN_N = 256  # above this token count, per-expert hipBLASLt GEMMs win
@@ -470,9 +472,12 @@ def _moe_prefill_gemm(x, gate_w, up_w, down_w, weights, indices,
 def moe_gate_subranges(router_logits_bf16, top_k: int,
                        routed_scaling_factor: float = 1.0,
                        norm_topk_prob: bool = False, max_tok: int = 4,
-                       n_group: int = 1, topk_group: int = 1):
+                       n_group: int = 1, topk_group: int = 1, *,
+                       scoring: str = "softmax", e_bias=None):
     """Fused gating: softmax + (group-limited) greedy top-k + expert sort
     + sub-range build in ONE kernel, with reference.moe_gate semantics.
+    scoring="sigmoid" with the optional fp32 [E] e_bias is DeepSeek-V3's
+    router (grouped: E/n_group >= 2).
 
     Limits (the binding raises outside them): N<=128 tokens, E<=256
     experts, k<=8, 1<=n_group<=32 with E % n_group == 0,
@@ -483,7 +488,8 @@ def moe_gate_subranges(router_logits_bf16, top_k: int,
     s_upper = E + (N * top_k) // max_tok
     return tuple(ext.moe_gate_subranges(router_logits_bf16, top_k, s_upper,
                                         max_tok, routed_scaling_factor,
-                                        norm_topk_prob, n_group, topk_group))
+                                        norm_topk_prob, n_group, topk_group,
+                                        scoring, e_bias))
 
 
 def moe_finalize(acc, shared, h):

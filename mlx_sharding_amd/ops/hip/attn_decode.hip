@@ -50,8 +50,8 @@ __global__ __launch_bounds__(AD_BLOCK) void attn_decode_kernel(
   const int hk = blockIdx.x % Hkv;
   const int split = blockIdx.y;
   const int nsplit = gridDim.y;
-  // Head-group split (gridDim.z): big-G shapes (absorbed MLA: 16 heads
-  // over one KV "head") run as NHG blocks of G heads each — smaller
+  // Head-group split (gridDim.z): big-G shapes (absorbed MLA: 16 to 128
+  // heads over one KV "head") run as NHG blocks of G heads each — smaller
   // per-block register state → real occupancy; the re-read K tile
   // stays L2-resident.  head id = hk*Gtot + hg*G + g.
   const int hg = blockIdx.z;
@@ -322,7 +322,11 @@ extern "C" void launch_attn_decode(const void* q, const void* q_rope,
   // tiles re-read from L2 by the sibling head-groups.  8-head groups
   // halve the K re-reads of the round-1 4-head choice at similar
   // occupancy (A/B'd on hardware).
-  const int G = (Gtot == 16 && DVT == 2) ? 8 : Gtot;  // 16: -2% (A/B)
+  // 32/64/128 heads (DeepSeek-V3 class MLA) reuse the same 8-head
+  // groups, Gtot / 8 of them, at either DVT (small-rank debug models
+  // have Dv <= 256); that width is untuned for those shapes.
+  const bool many = Gtot == 32 || Gtot == 64 || Gtot == 128;
+  const int G = (many || (Gtot == 16 && DVT == 2)) ? 8 : Gtot;  // 16: -2% (A/B)
   const int NHG = Gtot / G;
   const int nred = (G > AD_BLOCK / WAVE) ? G : AD_BLOCK / WAVE;
   size_t smem = (((size_t)G * Dk * sizeof(short) + 15) & ~(size_t)15) +
@@ -362,6 +366,8 @@ extern "C" void launch_attn_decode(const void* q, const void* q_rope,
 extern "C" bool attn_decode_supported_shape(int G, int Dv) {
   if (Dv > 512) return false;
   const int dvt = (Dv + AD_BLOCK - 1) / AD_BLOCK;
+  // 32/64/128 run as G / 8 head-groups of the 8-head instantiations
+  if (G == 32 || G == 64 || G == 128) return true;
   if (dvt == 2) return G == 16 || G == 4;
   return G == 1 || G == 2 || G == 4 || G == 6 || G == 7 || G == 8 ||
          G == 16;

@@ -76,9 +76,9 @@ void launch_moe_down_grouped(const void*, const void*, float*, const int*,
 void launch_moe_w4_mfma(const void*, const void*, const void*, const void*,
                         void*, const int*, const int*, const int*,
                         const int*, int, int, int, int, int, hipStream_t);
-void launch_moe_gate_subranges(const void*, int*, float*, int*, int*, int*,
-                               int, int, int, int, int, float, int, int, int,
-                               hipStream_t);
+void launch_moe_gate_subranges(const void*, const float*, int, int*, float*,
+                               int*, int*, int*, int, int, int, int, int,
+                               float, int, int, int, hipStream_t);
 void launch_moe_w4f16_gateup(const void*, const void*, const void*,
                              const void*, const void*, const void*,
                              const void*, void*, const int*, const int*,
@@ -871,8 +871,14 @@ std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
                                               int64_t s_upper, int64_t max_tok,
                                               double routed_scaling,
                                               bool norm_topk, int64_t n_group,
-                                              int64_t topk_group) {
+                                              int64_t topk_group,
+                                              const std::string& scoring,
+                                              c10::optional<torch::Tensor> e_bias) {
   check_bf16(logits, "logits");
+  TORCH_CHECK(scoring == "softmax" || scoring == "sigmoid",
+              "fused gate scoring must be 'softmax' or 'sigmoid' (got '",
+              scoring, "')");
+  const bool sigmoid = scoring == "sigmoid";
   TORCH_CHECK(logits.dim() == 2, "logits must be [N, E]");
   auto lc = logits.contiguous();
   const int64_t N = lc.size(0), E = lc.size(1);
@@ -891,6 +897,21 @@ std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
               topk_group, "*", E / n_group, " < ", K, ")");
   TORCH_CHECK(max_tok >= 1 && s_upper >= E + (N * K) / max_tok,
               "fused gate needs max_tok>=1 and s_upper >= E + N*K/max_tok");
+  // a sigmoid group is scored by its two best members
+  TORCH_CHECK(!sigmoid || n_group == 1 || E / n_group >= 2,
+              "fused gate limits: sigmoid scoring with groups needs "
+              "E/n_group >= 2 (got E=", E, ", n_group=", n_group, ")");
+  const float* bias_ptr = nullptr;
+  if (e_bias.has_value()) {
+    const torch::Tensor& eb = *e_bias;
+    TORCH_CHECK(sigmoid, "e_bias applies to sigmoid scoring only");
+    TORCH_CHECK(eb.scalar_type() == torch::kFloat32 && eb.is_contiguous() &&
+                    eb.device() == lc.device() && eb.dim() == 1 &&
+                    eb.size(0) == E,
+                "e_bias must be a contiguous fp32 [E] tensor on the logits' "
+                "device (E=", E, ")");
+    bias_ptr = eb.data_ptr<float>();
+  }
   const long P = (long)N * K;
   auto opts = torch::TensorOptions().dtype(torch::kInt32).device(lc.device());
   auto sorted_tok = torch::empty({P}, opts);
@@ -898,7 +919,8 @@ std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
   auto sub_expert = torch::empty({s_upper}, opts);
   auto sub_off = torch::empty({s_upper}, opts);
   auto sub_cnt = torch::empty({s_upper}, opts);
-  launch_moe_gate_subranges(lc.data_ptr(), sorted_tok.data_ptr<int>(),
+  launch_moe_gate_subranges(lc.data_ptr(), bias_ptr, sigmoid ? 1 : 0,
+                            sorted_tok.data_ptr<int>(),
                             sorted_wt.data_ptr<float>(),
                             sub_expert.data_ptr<int>(), sub_off.data_ptr<int>(),
                             sub_cnt.data_ptr<int>(), (int)N, (int)E, (int)K,
@@ -979,7 +1001,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("top_k"), pybind11::arg("s_upper"),
         pybind11::arg("max_tok"), pybind11::arg("routed_scaling"),
         pybind11::arg("norm_topk"), pybind11::arg("n_group") = 1,
-        pybind11::arg("topk_group") = 1);
+        pybind11::arg("topk_group") = 1,
+        pybind11::arg("scoring") = "softmax",
+        pybind11::arg("e_bias") = pybind11::none());
   m.def("moe_scatter_rows",
         [](torch::Tensor src, torch::Tensor dst, torch::Tensor src_idx,
            torch::Tensor dst_idx) {

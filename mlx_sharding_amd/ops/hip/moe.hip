@@ -437,6 +437,10 @@ extern "C" void launch_moe_gather_reduce(const void* d, const int* pos,
 // largest member probability, pick the top-k among their experts; the
 // weights stay the full-softmax probabilities).
 //
+// SIG = true is DeepSeek-V3's noaux_tc router: s = sigmoid(logit),
+// selection runs on c = s + e_bias (a group's score is the sum of its two
+// largest c, so E / n_group >= 2), the weights are the unbiased s.
+//
 // Single workgroup; one wave per token; lane l holds experts l, 64+l,
 // 128+l, 192+l in registers.  Limits (checked by the binding, the LDS
 // arrays are fixed-size): N <= 128 tokens, E <= 256 experts, top_k <= 8,
@@ -538,9 +542,10 @@ __device__ __forceinline__ void gk_sort_and_subranges(
 // 1024 threads (16 waves): the top-k argmax is a serial chain of
 // dependent ds_bpermute shuffles per token — more waves = fewer tokens
 // serialized per wave.  R = ceil(E / 64) probabilities per lane.
-template <int R>
+template <int R, bool SIG>
 __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
     const short* __restrict__ logits,  // [N, E] bf16
+    const float* __restrict__ e_bias,  // [E] fp32 or null (SIG only)
     int* __restrict__ sorted_tok,      // [P]
     float* __restrict__ sorted_wt,     // [P]
     int* __restrict__ sub_expert,      // [s_upper]
@@ -565,6 +570,10 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
   }
   __syncthreads();
 
+  // masked, padded and already-picked entries: below any probability
+  // (softmax), below any finite biased score (sigmoid; c can pass -1)
+  constexpr float NEG = SIG ? -__builtin_inff() : -1.0f;
+
   const int gsz = E / n_group;  // experts per group
   int grp[R];                   // group of this lane's r-th expert
 #pragma unroll
@@ -575,10 +584,22 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
   for (int t0 = 0; t0 < N; t0 += GK_WAVES) {
     const int t = t0 + wid;
     const bool live = t < N;
-    float p[R];
+    float p[R];            // selection score: probability, or c (SIG)
+    float s[SIG ? R : 1];  // SIG: unbiased sigmoid score, the weight
 #pragma unroll
     for (int r = 0; r < R; ++r) p[r] = 0.0f;
-    if (live) {
+    if constexpr (SIG) {
+      if (live) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int e = r * WAVE + lane;
+          const int ec = min(e, E - 1);  // padded lanes are masked below
+          const float x = bfbits2f(logits[(long)t * E + ec]);
+          s[r] = 1.0f / (1.0f + __expf(-x));
+          p[r] = s[r] + (e_bias ? e_bias[ec] : 0.0f);
+        }
+      }
+    } else if (live) {
       float sc[R];
       float mx = -1e30f;
 #pragma unroll
@@ -609,13 +630,24 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
       }
       __syncthreads();
       if (live) {
-        // lane g scans group g for its max probability; -1 marks lanes
-        // without a group and groups already kept
-        float gs = -1.0f;
+        // lane g scans group g for its max probability (SIG: the sum of
+        // its two largest c); NEG marks lanes without a group and groups
+        // already kept
+        float gs = NEG;
         if (lane < n_group) {
           const float* row = &probs[wid][lane * gsz];
-          gs = row[0];
-          for (int j = 1; j < gsz; ++j) gs = fmaxf(gs, row[j]);
+          if constexpr (SIG) {
+            float b1 = NEG, b2 = NEG;
+            for (int j = 0; j < gsz; ++j) {
+              const float v = row[j];
+              if (v > b1) { b2 = b1; b1 = v; }
+              else if (v > b2) b2 = v;
+            }
+            gs = b1 + b2;  // gsz >= 2: both finite
+          } else {
+            gs = row[0];
+            for (int j = 1; j < gsz; ++j) gs = fmaxf(gs, row[j]);
+          }
         }
         gmask = 0u;
         for (int g = 0; g < topk_group; ++g) {
@@ -623,20 +655,20 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
           int bidx = lane;
           gk_wave_argmax(best, bidx);
           gmask |= 1u << bidx;
-          if (lane == bidx) gs = -1.0f;
+          if (lane == bidx) gs = NEG;
         }
       }
       __syncthreads();  // row is rewritten by the next token
     }
 
     if (live) {
-      // masked, padded and already-picked experts sit at -1, below any
-      // probability (an unmasked probability that underflowed to 0 wins)
+      // masked, padded and already-picked experts sit at NEG (an
+      // unmasked probability that underflowed to 0 wins)
       float psel[R];
 #pragma unroll
       for (int r = 0; r < R; ++r)
         psel[r] = (r * WAVE + lane < E && ((gmask >> grp[r]) & 1u)) ? p[r]
-                                                                    : -1.0f;
+                                                                    : NEG;
       float wsum = 0.0f;
 #pragma unroll
       for (int k = 0; k < GK_MAXK; ++k) {
@@ -648,6 +680,14 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
         for (int r = 1; r < R; ++r)
           if (psel[r] > best) { best = psel[r]; bidx = r * WAVE + lane; }
         gk_wave_argmax(best, bidx);
+        if constexpr (SIG) {
+          // selection ran on c; the weight is the owner lane's s
+          float sv = s[0];
+#pragma unroll
+          for (int r = 1; r < R; ++r)
+            if (bidx / WAVE == r) sv = s[r];
+          best = __shfl(sv, bidx & (WAVE - 1), WAVE);
+        }
         if (lane == 0) {
           tok_e[t * GK_MAXK + k] = bidx;
           tok_w[t * GK_MAXK + k] = best;
@@ -656,7 +696,7 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
         wsum += best;
 #pragma unroll
         for (int r = 0; r < R; ++r)
-          if (bidx == r * WAVE + lane) psel[r] = -1.0f;
+          if (bidx == r * WAVE + lane) psel[r] = NEG;
       }
       if (norm_topk && lane == 0) {
 #pragma unroll
@@ -675,23 +715,30 @@ __global__ __launch_bounds__(1024) void moe_gate_subranges_kernel(
 }
 
 extern "C" void launch_moe_gate_subranges(
-    const void* logits, int* sorted_tok, float* sorted_wt, int* sub_expert,
-    int* sub_off, int* sub_cnt, int N, int E, int K, int s_upper, int max_tok,
-    float routed_scaling, int norm_topk, int n_group, int topk_group,
-    hipStream_t stream) {
+    const void* logits, const float* e_bias, int sigmoid, int* sorted_tok,
+    float* sorted_wt, int* sub_expert, int* sub_off, int* sub_cnt, int N,
+    int E, int K, int s_upper, int max_tok, float routed_scaling,
+    int norm_topk, int n_group, int topk_group, hipStream_t stream) {
   // limits are checked by the caller (bindings.hip::moe_gate_subranges)
-#define GK_LAUNCH(R)                                                         \
-  moe_gate_subranges_kernel<R>                                               \
+#define GK_LAUNCH(R, SIG)                                                    \
+  moe_gate_subranges_kernel<R, SIG>                                          \
       <<<dim3(1), dim3(GK_WAVES * WAVE), 0, stream>>>(                       \
-          (const short*)logits, sorted_tok, sorted_wt, sub_expert, sub_off,  \
-          sub_cnt, N, E, K, s_upper, max_tok, routed_scaling, norm_topk,     \
-          n_group, topk_group)
-  switch ((E + WAVE - 1) / WAVE) {
-    case 1: GK_LAUNCH(1); break;
-    case 2: GK_LAUNCH(2); break;
-    case 3: GK_LAUNCH(3); break;
-    default: GK_LAUNCH(4); break;
+          (const short*)logits, e_bias, sorted_tok, sorted_wt, sub_expert,   \
+          sub_off, sub_cnt, N, E, K, s_upper, max_tok, routed_scaling,       \
+          norm_topk, n_group, topk_group)
+#define GK_SWITCH(SIG)                                                       \
+  switch ((E + WAVE - 1) / WAVE) {                                           \
+    case 1: GK_LAUNCH(1, SIG); break;                                        \
+    case 2: GK_LAUNCH(2, SIG); break;                                        \
+    case 3: GK_LAUNCH(3, SIG); break;                                        \
+    default: GK_LAUNCH(4, SIG); break;                                       \
   }
+  if (sigmoid) {
+    GK_SWITCH(true)
+  } else {
+    GK_SWITCH(false)
+  }
+#undef GK_SWITCH
 #undef GK_LAUNCH
 }
 

@@ -253,13 +253,24 @@ def quantized_linear(x: torch.Tensor, w_q: torch.Tensor, scales: torch.Tensor,
 
 def moe_gate(router_logits: torch.Tensor, top_k: int, n_group: int = 1,
              topk_group: int = 1, routed_scaling_factor: float = 1.0,
-             norm_topk_prob: bool = False):
+             norm_topk_prob: bool = False, *, scoring: str = "softmax",
+             e_bias: Optional[torch.Tensor] = None):
     """Softmax router → group-limited greedy top-k.
 
     router_logits: [N, E].  Returns (weights [N, top_k], indices [N, top_k]).
     Matches DeepSeek-V2 MoEGate (greedy scoring_func=softmax,
     topk_method=greedy/group_limited_greedy).
+
+    scoring="sigmoid" is DeepSeek-V3's noaux_tc router instead (see
+    _moe_gate_sigmoid); e_bias is its per-expert selection bias.
     """
+    if scoring == "sigmoid":
+        return _moe_gate_sigmoid(router_logits, top_k, n_group, topk_group,
+                                 routed_scaling_factor, norm_topk_prob, e_bias)
+    if scoring != "softmax":
+        raise ValueError(f"moe_gate: unknown scoring {scoring!r}")
+    if e_bias is not None:
+        raise ValueError("moe_gate: e_bias applies to sigmoid scoring only")
     scores = torch.softmax(router_logits.float(), dim=-1)
     N, E = scores.shape
     if n_group > 1:
@@ -271,6 +282,35 @@ def moe_gate(router_logits: torch.Tensor, top_k: int, n_group: int = 1,
         mask = gmask[:, :, None].expand(N, n_group, E // n_group).reshape(N, E)
         scores = scores.masked_fill(~mask, 0.0)
     weights, indices = torch.topk(scores, k=top_k, dim=-1)
+    if norm_topk_prob:
+        weights = weights / (weights.sum(-1, keepdim=True) + 1e-20)
+    weights = weights * routed_scaling_factor
+    return weights, indices
+
+
+def _moe_gate_sigmoid(router_logits, top_k, n_group, topk_group,
+                      routed_scaling_factor, norm_topk_prob, e_bias):
+    """DeepSeek-V3 noaux_tc gate, all in fp32: s = sigmoid(logits) are the
+    weights; selection runs on c = s + e_bias.  A group's score is the sum
+    of its two largest c; experts outside the topk_group best groups are
+    masked with -inf (c can be negative)."""
+    s = torch.sigmoid(router_logits.float())
+    N, E = s.shape
+    c = s if e_bias is None else s + e_bias.float().to(s.device)
+    if n_group > 1:
+        gsz = E // n_group
+        if gsz < 2:
+            raise ValueError(
+                f"moe_gate: sigmoid scoring needs E/n_group >= 2 "
+                f"(got E={E}, n_group={n_group})")
+        group_top = c.reshape(N, n_group, gsz).topk(2, dim=-1).values.sum(-1)
+        top_groups = torch.topk(group_top, k=topk_group, dim=-1).indices
+        gmask = torch.zeros(N, n_group, device=s.device, dtype=torch.bool)
+        gmask.scatter_(1, top_groups, True)
+        mask = gmask[:, :, None].expand(N, n_group, gsz).reshape(N, E)
+        c = c.masked_fill(~mask, float("-inf"))
+    indices = torch.topk(c, k=top_k, dim=-1).indices
+    weights = s.gather(1, indices)
     if norm_topk_prob:
         weights = weights / (weights.sum(-1, keepdim=True) + 1e-20)
     weights = weights * routed_scaling_factor

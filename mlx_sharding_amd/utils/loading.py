@@ -158,7 +158,10 @@ def load_model(model_path: str | Path,
     model = cls(config, shard, quant_for=quant_for)
     if dtype is not None:
         for k in list(weights):
-            if weights[k].is_floating_point():
+            # the V3 router's selection bias stays fp32 whatever the model
+            # dtype (rounding it can change which experts are picked)
+            if (weights[k].is_floating_point()
+                    and not k.endswith("e_score_correction_bias")):
                 weights[k] = weights[k].to(dtype)
     model.load_weights(weights)
     model.to(device)

@@ -52,11 +52,58 @@ def bench_grouped_gate(ops, ref, iters, dev="cuda"):
           f"({t_torch / t_fused:.1f}x)")
 
 
+def _repeat(fn, iters, repeats=5):
+    """(median, min, max) us over `repeats` timed windows."""
+    ts = sorted(timeit(fn, iters, warmup=20) for _ in range(repeats))
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def bench_v3(ops, ext, dev="cuda"):
+    """DeepSeek-V3 shapes: the fused gate at E=256 in softmax
+    group-limited mode vs sigmoid mode (alternated, same process), and
+    128-head absorbed decode attention at B=64."""
+    N, E, K, n_group, topk_group = 64, 256, 8, 8, 4
+    g = torch.Generator().manual_seed(1)
+    logits = torch.randn(N, E, generator=g).to(torch.bfloat16).to(dev)
+    bias = (torch.rand(E, generator=g) * 2.0 - 1.5).to(dev)
+
+    def softmax():
+        return ops.moe_gate_subranges(logits, K, 2.5, True, max_tok=16,
+                                      n_group=n_group, topk_group=topk_group)
+
+    def sigmoid():
+        return ops.moe_gate_subranges(logits, K, 2.5, True, max_tok=16,
+                                      n_group=n_group, topk_group=topk_group,
+                                      scoring="sigmoid", e_bias=bias)
+
+    for rnd in range(2):  # alternate the two modes
+        for name, fn in (("softmax", softmax), ("sigmoid", sigmoid)):
+            med, lo, hi = _repeat(fn, 3000)
+            print(f"moe_gate_subranges N=64 E=256 g8/4 k=8 {name:8s} "
+                  f"round {rnd}: median {med:7.2f} us  "
+                  f"min {lo:7.2f}  max {hi:7.2f}")
+
+    B, Hq, Dk, Dv = 64, 128, 576, 512
+    q = torch.randn(B, Hq, 1, Dk, dtype=torch.bfloat16, device=dev)
+    for S in (512, 4096):
+        kbuf = torch.randn(B, 1, S, Dk, dtype=torch.bfloat16, device=dev)
+        v = kbuf[..., :Dv]
+        med, lo, hi = _repeat(
+            lambda: ext.attn_decode(q, kbuf, v, Dk ** -0.5, 0.0, 0, None), 200)
+        kv_bytes = B * S * Dk * 2
+        print(f"attn_decode/abs Hq=128 B=64 S={S:5d}: median {med:8.1f} us  "
+              f"min {lo:8.1f}  max {hi:8.1f}  "
+              f"~{kv_bytes / (med / 1e6) / 1e12:.2f} TB/s of one K pass")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--gate-only", action="store_true",
                     help="only the grouped-gating fused-vs-torch line")
+    ap.add_argument("--v3-only", action="store_true",
+                    help="only the DeepSeek-V3 gate and 128-head attention "
+                         "lines")
     args = ap.parse_args()
     from mlx_sharding_amd import ops
     from mlx_sharding_amd.ops import reference as ref
@@ -67,6 +114,9 @@ def main():
 
     if args.gate_only:
         bench_grouped_gate(ops, ref, args.iters, dev)
+        return
+    if args.v3_only:
+        bench_v3(ops, ext, dev)
         return
 
     E, H, I, N, K = 64, 2048, 1408, 64, 6
