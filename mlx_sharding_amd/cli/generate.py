@@ -11,6 +11,8 @@ import argparse
 
 import torch
 
+from . import quantize_choice, quantize_request
+
 
 def main(argv=None):
     p = argparse.ArgumentParser(description="LLM pipeline inference")
@@ -27,8 +29,10 @@ def main(argv=None):
                    help="sampling temperature (0 = greedy, the reference CLI default)")
     p.add_argument("--device", type=str,
                    default="cuda" if torch.cuda.is_available() else "cpu")
-    p.add_argument("--quantize", type=int, choices=[4, 8], default=None,
-                   help="quantize a dense checkpoint to w4a16/w8a16 at load")
+    p.add_argument("--quantize", type=quantize_choice, default=None,
+                   metavar="{4,8,fp8}",
+                   help="quantize a dense checkpoint to w4a16/w8a16 (or fp8: FP8 "
+                        "128x128 blocks) at load")
     p.add_argument("--quantize-group-size", type=int, default=64)
     args = p.parse_args(argv)
 
@@ -43,7 +47,7 @@ def main(argv=None):
     # local directory or HF repo id (reference utils.py:33-39)
     path = get_model_path(args.model)
     tokenizer = AutoTokenizer.from_pretrained(str(path))
-    q = (args.quantize, args.quantize_group_size) if args.quantize else None
+    q = quantize_request(args.quantize, args.quantize_group_size)
     model, config = load_model(path, args.start_layer, args.end_layer,
                                device=args.device, quantize=q)
     remotes = make_clients(args.server_address.split(",")) if args.server_address else []

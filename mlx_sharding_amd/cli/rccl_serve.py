@@ -10,14 +10,18 @@ from __future__ import annotations
 
 import argparse
 
+from . import quantize_choice, quantize_request
+
 
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--model", type=str, required=True)
     p.add_argument("--host", type=str, default="127.0.0.1")
     p.add_argument("--port", type=int, default=8080)
-    p.add_argument("--quantize", type=int, choices=[4, 8], default=None,
-                   help="quantize a dense checkpoint to w4a16/w8a16 at load "
+    p.add_argument("--quantize", type=quantize_choice, default=None,
+                   metavar="{4,8,fp8}",
+                   help="quantize a dense checkpoint to w4a16/w8a16 (or fp8: FP8 "
+                        "128x128 blocks) at load "
                         "(the fast path on MI355X)")
     p.add_argument("--quantize-group-size", type=int, default=64)
     from ..parallel.batching import MAX_BATCH_LIMIT, env_max_batch
@@ -43,7 +47,7 @@ def main(argv=None):
                          "model; launch rccl-serve with one rank")
     cfg = ModelConfig.load(args.model)
     s, e = split_layers(cfg.num_hidden_layers, world)[rank]
-    q = (args.quantize, args.quantize_group_size) if args.quantize else None
+    q = quantize_request(args.quantize, args.quantize_group_size)
     model, _ = load_model(args.model, s, e, device=str(device), quantize=q)
     worker = PipelineWorker(model, rank, world, device)
     pipeline = RcclPipeline(worker)

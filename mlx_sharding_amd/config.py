@@ -48,20 +48,62 @@ class ShardSpec:
 
 @dataclass
 class QuantConfig:
-    """MLX-style affine quantization stanza from config.json.
+    """Quantization stanza from config.json.
 
-    w = scales * q + biases, per group of `group_size` input elements;
-    q packed little-endian into uint32 (8 nibbles per word at bits=4).
-    Matches the checkpoint format the reference loads via
-    /root/reference/shard/utils.py:54-65.
+    fmt "affine" (MLX-style): w = scales * q + biases, per group of
+    `group_size` input elements; q packed little-endian into uint32
+    (8 nibbles per word at bits=4).  Matches the checkpoint format the
+    reference loads via /root/reference/shard/utils.py:54-65.
+
+    fmt "fp8_block" (DeepSeek-V3/R1 originals): `weight` is
+    float8_e4m3fn [O, K] and `weight_scale_inv` fp32
+    [ceil(O/gs), ceil(K/gs)] holds one scale per gs x gs block,
+    w[o, k] = float(weight[o, k]) * weight_scale_inv[o // gs, k // gs];
+    bits=8 and group_size=128 (the block edge).
     """
 
     group_size: int = 64
     bits: int = 4
+    fmt: str = "affine"
+
+    def __post_init__(self):
+        if self.fmt not in ("affine", "fp8_block"):
+            raise ValueError(f"QuantConfig: unknown fmt {self.fmt!r}")
+        if self.fmt == "fp8_block" and (self.bits != 8
+                                        or self.group_size != 128):
+            raise ValueError(
+                "QuantConfig: fp8_block needs bits=8 and group_size=128 "
+                f"(got bits={self.bits}, group_size={self.group_size})")
 
     @classmethod
     def from_dict(cls, d: dict) -> "QuantConfig":
         return cls(group_size=int(d.get("group_size", 64)), bits=int(d.get("bits", 4)))
+
+    @classmethod
+    def from_hf_fp8(cls, d: dict) -> "QuantConfig":
+        """The `quantization_config` stanza of an FP8 checkpoint
+        (quant_method == "fp8").  Only e4m3 weights in 128x128 blocks
+        with dynamic (or unspecified) activation scaling are supported."""
+        fmt = d.get("fmt", "e4m3")
+        if fmt != "e4m3":
+            raise ValueError(
+                f"quantization_config: fmt {fmt!r} not supported (only 'e4m3')")
+        wbs = d.get("weight_block_size")
+        if wbs is None or list(wbs) != [128, 128]:
+            raise ValueError(
+                f"quantization_config: weight_block_size {wbs!r} not "
+                f"supported (only [128, 128])")
+        act = d.get("activation_scheme")
+        if act not in (None, "dynamic"):
+            raise ValueError(
+                f"quantization_config: activation_scheme {act!r} not "
+                f"supported (only 'dynamic')")
+        return cls(group_size=128, bits=8, fmt="fp8_block")
+
+
+FP8_QUANTIZATION_CONFIG = {"quant_method": "fp8", "fmt": "e4m3",
+                           "activation_scheme": "dynamic",
+                           "weight_block_size": [128, 128]}
 
 
 @dataclass
@@ -84,7 +126,12 @@ class ModelConfig:
     @property
     def quantization(self) -> Optional[QuantConfig]:
         q = self.raw.get("quantization")
-        return QuantConfig.from_dict(q) if q else None
+        if q:
+            return QuantConfig.from_dict(q)
+        hf = self.raw.get("quantization_config")
+        if hf and hf.get("quant_method") == "fp8":
+            return QuantConfig.from_hf_fp8(hf)
+        return None
 
     @property
     def start_layer(self) -> int:

@@ -23,6 +23,19 @@ from ..ops.kvcache import KVCache
 QuantPredicate = Callable[[str], bool]
 
 
+def fp8_block_params(shape, block: int = 128):
+    """(weight, weight_scale_inv) parameters of an FP8 block-quantized
+    matrix of the given [.., O, K] shape: float8_e4m3fn weights and one
+    fp32 scale per block x block tile (partial last tiles included)."""
+    *lead, O, K = shape
+    weight = nn.Parameter(torch.empty(*shape, dtype=torch.float8_e4m3fn),
+                          requires_grad=False)
+    scale_inv = nn.Parameter(
+        torch.empty(*lead, -(-O // block), -(-K // block),
+                    dtype=torch.float32), requires_grad=False)
+    return weight, scale_inv
+
+
 class Linear(nn.Module):
     """Dense or MLX-affine-quantized linear, chosen per checkpoint key.
 
@@ -30,7 +43,9 @@ class Linear(nn.Module):
     w4a16/w8a16 dequant-GEMM op.  Parameter names (weight/scales/biases)
     match the MLX checkpoint layout so pre-quantized checkpoints load
     directly (/root/reference/shard/utils.py:54-65 predicate: a
-    `.scales` key exists for the module).
+    `.scales` key exists for the module).  Under the fp8_block format the
+    parameters are `weight` (float8_e4m3fn) and `weight_scale_inv` (fp32
+    block scales) — the FP8 checkpoints' names — with no scales/biases.
     """
 
     def __init__(self, in_features: int, out_features: int,
@@ -43,6 +58,10 @@ class Linear(nn.Module):
         if quant is None:
             self.weight = nn.Parameter(
                 torch.empty(out_features, in_features, dtype=dtype), requires_grad=False)
+        elif quant.fmt == "fp8_block":
+            # the FP8 checkpoint's own names: weight + weight_scale_inv
+            self.weight, self.weight_scale_inv = fp8_block_params(
+                (out_features, in_features), quant.group_size)
         else:
             per_word = 32 // quant.bits
             wdtype = torch.uint32 if hasattr(torch, "uint32") else torch.int32
@@ -64,8 +83,11 @@ class Linear(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.quant is None:
             return ops.linear(x, self.weight, self.bias)
-        y = ops.quantized_linear(x, self.weight, self.scales, self.biases,
-                                 self.quant.group_size, self.quant.bits)
+        if self.quant.fmt == "fp8_block":
+            y = ops.fp8_block_linear(x, self.weight, self.weight_scale_inv)
+        else:
+            y = ops.quantized_linear(x, self.weight, self.scales, self.biases,
+                                     self.quant.group_size, self.quant.bits)
         if self.bias is not None:
             y = y + self.bias
         return y
@@ -139,8 +161,17 @@ class StageModel(nn.Module):
         """Activation dtype = first floating parameter's dtype (a packed
         uint32 quant weight can come first on stages without embeddings
         — casting activations to THAT truncates them to garbage)."""
-        return next((q.dtype for q in self.parameters()
-                     if q.is_floating_point()), torch.bfloat16)
+        fp = self._first_fp_param()
+        return fp.dtype if fp is not None else torch.bfloat16
+
+    def _first_fp_param(self):
+        """First parameter in the activation dtype: floating, but neither
+        an FP8 weight nor its fp32 block scales."""
+        for name, q in self.named_parameters():
+            if (q.is_floating_point() and q.element_size() > 1
+                    and not name.endswith("weight_scale_inv")):
+                return q
+        return None
 
     # -- cache ------------------------------------------------------------
     def cache_specs(self) -> List[Tuple[int, int, int]]:
@@ -154,7 +185,8 @@ class StageModel(nn.Module):
         # weight, and a uint32 KV cache silently truncates every K/V
         # value to zero (caught as PP-parity divergence)
         p = next(self.parameters())
-        fp = next((q for q in self.parameters() if q.is_floating_point()), p)
+        fp = self._first_fp_param()
+        fp = fp if fp is not None else p
         from ..ops.kvcache import make_cache
         return make_cache(self.cache_specs(),
                           dtype=dtype or fp.dtype,

@@ -17,7 +17,8 @@ import torch.nn as nn
 from .. import ops
 from ..config import ModelConfig, QuantConfig, ShardSpec
 from ..ops.kvcache import KVCache
-from .base import Linear, RMSNorm, StageModel, owned_layer_indices
+from .base import (Linear, RMSNorm, StageModel, fp8_block_params,
+                   owned_layer_indices)
 from .llama import LlamaMLP, _Inner
 
 
@@ -38,11 +39,22 @@ class SwitchMLP(nn.Module):
         self.up_proj = _StackedLinear(n_experts, hidden, inter, quant, dtype)
         self.down_proj = _StackedLinear(n_experts, inter, hidden, quant, dtype)
 
+    @property
+    def _fp8(self) -> bool:
+        return self.quant is not None and self.quant.fmt == "fp8_block"
+
+    def _fp8_pairs(self):
+        """(weight, weight_scale_inv) of gate, up and down."""
+        return tuple((p.weight, p.weight_scale_inv)
+                     for p in (self.gate_proj, self.up_proj, self.down_proj))
+
     def resident_dense(self):
         """Budget-capped resident bf16 expert copies for quant decode
         (ops.expert_dequant_resident; None when memory-tight)."""
         if self.quant is None:
             return None
+        if self._fp8:
+            return ops.expert_dequant_fp8_resident(*self._fp8_pairs())
         g, u, d = self.gate_proj, self.up_proj, self.down_proj
         return ops.expert_dequant_resident(
             (g.weight, g.scales, g.biases),
@@ -67,6 +79,9 @@ class SwitchMLP(nn.Module):
                     return ops.grouped_expert_mlp_subs(
                         x_flat, dense[0], dense[1], dense[2], subs, max_tok,
                         raw=raw)
+            if self._fp8:
+                return ops.grouped_expert_mlp_fp8_subs(
+                    x_flat, *self._fp8_pairs(), subs, raw=raw)
             g, u, d = self.gate_proj, self.up_proj, self.down_proj
             return ops.grouped_expert_mlp_quant_subs(
                 x_flat,
@@ -80,6 +95,9 @@ class SwitchMLP(nn.Module):
 
     def forward(self, x_flat: torch.Tensor, weights: torch.Tensor,
                 indices: torch.Tensor) -> torch.Tensor:
+        if self._fp8:
+            return ops.grouped_expert_mlp_fp8(x_flat, *self._fp8_pairs(),
+                                              weights, indices)
         if self.quant is not None:
             g, u, d = self.gate_proj, self.up_proj, self.down_proj
             return ops.grouped_expert_mlp_quant(
@@ -104,6 +122,9 @@ class _StackedLinear(nn.Module):
             self.weight = nn.Parameter(
                 torch.empty(E, out_features, in_features, dtype=dtype),
                 requires_grad=False)
+        elif quant.fmt == "fp8_block":
+            self.weight, self.weight_scale_inv = fp8_block_params(
+                (E, out_features, in_features), quant.group_size)
         else:
             per_word = 32 // quant.bits
             wdtype = torch.uint32 if hasattr(torch, "uint32") else torch.int32
@@ -120,6 +141,8 @@ class _StackedLinear(nn.Module):
     def dense(self) -> torch.Tensor:
         if self.quantc is None:
             return self.weight
+        if self.quantc.fmt == "fp8_block":
+            return ops.dequantize_fp8_block(self.weight, self.weight_scale_inv)
         outs = [ops.dequantize(self.weight[e], self.scales[e], self.biases[e],
                                self.quantc.group_size, self.quantc.bits)
                 for e in range(self.weight.shape[0])]
@@ -195,7 +218,10 @@ class MLAAttention(nn.Module):
         if self._w_uk is not None:
             return
         w = self.kv_b_proj.weight
-        if self.kv_b_proj.quant is not None:
+        if (self.kv_b_proj.quant is not None
+                and self.kv_b_proj.quant.fmt == "fp8_block"):
+            w = ops.dequantize_fp8_block(w, self.kv_b_proj.weight_scale_inv)
+        elif self.kv_b_proj.quant is not None:
             qc = self.kv_b_proj.quant
             w = ops.dequantize(w, self.kv_b_proj.scales, self.kv_b_proj.biases,
                                qc.group_size, qc.bits)

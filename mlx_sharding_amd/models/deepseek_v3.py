@@ -10,7 +10,11 @@ up to 128 heads.
 Checkpoints in the MLX / HF layout load directly: per-expert
 `mlp.experts.E.*` stack into `switch_mlp.*`, `rotary_emb.inv_freq` and
 the multi-token-prediction layers (`model.layers.i.*`, i >=
-num_hidden_layers) are dropped.
+num_hidden_layers) are dropped.  The published FP8 block-quantized
+checkpoints load the same way: `X.weight` (float8_e4m3fn) and
+`X.weight_scale_inv` (fp32, one scale per 128x128 block) are the module
+parameters' own names, per-expert scales stack to [E, RB, KB], and the
+FP8 multi-token-prediction layers are dropped with the rest.
 """
 
 from __future__ import annotations

@@ -23,6 +23,16 @@ class FusedColumns:
 
     def __init__(self, linears: Sequence[Linear]):
         assert len({l.in_features for l in linears}) == 1
+        fp8 = [l.quant is not None and l.quant.fmt == "fp8_block"
+               for l in linears]
+        if any(fp8):
+            # block scales follow 128-row blocks of the CONCATENATED
+            # weight, so every part but the last must end on a block
+            # edge; checked before anything is mutated
+            assert all(fp8), "mixed fp8_block / other group"
+            assert all(l.out_features % l.quant.group_size == 0
+                       for l in linears[:-1]), \
+                "fp8_block part does not end on a scale-block edge"
         # all-or-nothing bias (qwen2 QKV all carry biases; mixed groups
         # are rejected and left unfused by fuse_model's except)
         has_bias = [l.bias is not None for l in linears]
@@ -47,7 +57,16 @@ class FusedColumns:
             l.weight.data = w[off: off + l.weight.shape[0]]
             off += l.weight.shape[0]
         self.weight = w
-        if self.quant is not None:
+        if self.quant is not None and self.quant.fmt == "fp8_block":
+            s = torch.cat([l.weight_scale_inv.data for l in linears],
+                          dim=0).contiguous()
+            off = 0
+            for l in linears:
+                n = l.weight_scale_inv.shape[0]
+                l.weight_scale_inv.data = s[off: off + n]
+                off += n
+            self.weight_scale_inv = s
+        elif self.quant is not None:
             s = torch.cat([l.scales.data for l in linears], dim=0).contiguous()
             b = torch.cat([l.biases.data for l in linears], dim=0).contiguous()
             off = 0
@@ -61,6 +80,10 @@ class FusedColumns:
     def __call__(self, x: torch.Tensor) -> List[torch.Tensor]:
         if self.quant is None:
             y = ops.linear(x, self.weight, self.bias)
+        elif self.quant.fmt == "fp8_block":
+            y = ops.fp8_block_linear(x, self.weight, self.weight_scale_inv)
+            if self.bias is not None:
+                y = y + self.bias
         else:
             y = ops.quantized_linear(x, self.weight, self.scales, self.biases,
                                      self.quant.group_size, self.quant.bits)

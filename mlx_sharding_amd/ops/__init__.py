@@ -328,6 +328,48 @@ def quantized_linear(x, w_q, scales, biases, group_size: int, bits: int):
     return ref.quantized_linear(x, w_q, scales, biases, group_size, bits)
 
 
+def _fp8_kernel_ok(w8, scale_inv) -> bool:
+    """The fp8_block.hip kernels' preconditions: K % 128 == 0 and
+    contiguous tensors (O is arbitrary)."""
+    return (w8.shape[-1] % 128 == 0 and w8.is_contiguous()
+            and scale_inv.is_contiguous())
+
+
+def dequantize_fp8_block(w8, scale_inv):
+    """FP8 block-quantized weight [O, K] / [E, O, K] -> dense: bf16 in one
+    kernel launch on GPU, the fp32 reference on CPU."""
+    if _use_hip(w8):
+        return _require_ext("dequantize_fp8_block").fp8_block_dequant(
+            w8.contiguous(), scale_inv.contiguous())
+    return ref.dequantize_fp8_block(w8, scale_inv)
+
+
+def fp8_block_linear(x, w8, scale_inv):
+    """y = x @ W^T for an FP8 block-quantized W (W8A16).  GPU policy is
+    quantized_linear's: a resident bf16 copy under the dq-cache budget,
+    else the fp8 GEMV kernel for M <= 64, else dequant per call."""
+    if _use_hip(x):
+        ext = _require_ext("fp8_block_linear")
+        lead = x.shape[:-1]
+        K = x.shape[-1]
+        x2 = x.reshape(-1, K)
+        M = x2.shape[0]
+        w = getattr(w8, "_mlxs_dqw", None)
+        if w is None and _dq_cache_ok(w8.shape[0] * K * 2):
+            w = dequantize_fp8_block(w8, scale_inv)
+            w8._mlxs_dqw = w
+        if w is not None:
+            y = linear(x2, w.to(x2.dtype))
+        elif 0 < M <= _GEMV_MAX_M and _fp8_kernel_ok(w8, scale_inv):
+            y = ext.fp8f16_gemv(_to_f16_cached(x).reshape(-1, K), w8,
+                                scale_inv).to(x2.dtype)
+        else:
+            w = dequantize_fp8_block(w8, scale_inv)
+            y = torch.nn.functional.linear(x2, w.to(x2.dtype))
+        return y.reshape(*lead, y.shape[-1])
+    return ref.fp8_block_linear(x, w8, scale_inv)
+
+
 def moe_gate(router_logits, top_k: int, n_group: int = 1, topk_group: int = 1,
              routed_scaling_factor: float = 1.0, norm_topk_prob: bool = False,
              *, scoring: str = "softmax", e_bias=None):
@@ -697,6 +739,85 @@ def grouped_expert_mlp_quant(x, gate, up, down, weights, indices,
     return ref.grouped_expert_mlp(x, gw, uw, dw, weights, indices)
 
 
+def expert_dequant_fp8(gate, up, down):
+    """Dequantize stacked FP8 expert (w8, scale_inv) pairs to bf16, cached
+    on the gate weight under the dq-cache budget (expert_dequant's
+    policy).  Returns (gate_w, up_w, down_w) dense [E, *, *]."""
+    cached = getattr(gate[0], "_mlxs_dq", None)
+    if cached is not None:
+        return cached
+    res = tuple(dequantize_fp8_block(w, s) for w, s in (gate, up, down))
+    if _dq_cache_ok(sum(t.numel() * 2 for t in res)):
+        gate[0]._mlxs_dq = res
+    return res
+
+
+def expert_dequant_fp8_resident(gate, up, down):
+    """The cached dense triplet if the budget allows holding it (built on
+    first call), else None."""
+    cached = getattr(gate[0], "_mlxs_dq", None)
+    if cached is not None:
+        return cached
+    est = 2 * (gate[0].numel() + up[0].numel() + down[0].numel())
+    cap = _dq_cache_cap()
+    if cap is None or _DQ_CACHE_BYTES + est > cap:
+        return None
+    res = expert_dequant_fp8(gate, up, down)
+    return res if getattr(gate[0], "_mlxs_dq", None) is not None else None
+
+
+def grouped_expert_mlp_fp8_subs(x, gate, up, down, subs, raw: bool = False):
+    """FP8 block-quantized grouped experts over prebuilt 16-token
+    sub-ranges via the packed W8A16 MFMA kernels (fp8_block.hip): fused
+    gate+up+SiLU, then down with the weighted scatter.  gate/up/down are
+    (w8 [E, ., .], weight_scale_inv) pairs; activations are cast to fp16
+    (see _to_f16_cached).  Shapes outside the kernels' limits
+    (K % 128 != 0) run the dense sub-range kernels on a dequantized
+    copy."""
+    ext = _require_ext("grouped_expert_mlp_fp8")
+    if not (_fp8_kernel_ok(*gate) and _fp8_kernel_ok(*up)
+            and _fp8_kernel_ok(*down)):
+        gw, uw, dw = expert_dequant_fp8(gate, up, down)
+        return grouped_expert_mlp_subs(x, gw.to(x.dtype), uw.to(x.dtype),
+                                       dw.to(x.dtype), subs, 16, raw=raw)
+    sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt = subs
+    P = sorted_tok.shape[0]
+    N = x.shape[0]
+    x16 = _to_f16_cached(x)
+    if raw:
+        # the gate+up launch zeroes the down kernel's accumulator; the
+        # caller finishes with moe_finalize
+        hh, acc = ext.moe_fp8f16_gateup_acc(
+            x16, gate[0], up[0], gate[1], up[1], sub_e, sub_off, sub_cnt,
+            sorted_tok, P, N, down[0].shape[1])
+        return ext.moe_fp8f16_down(hh, down[0], down[1], sub_e, sub_off,
+                                   sub_cnt, sorted_tok, sorted_wt, N, acc)
+    hh = ext.moe_fp8f16_gateup(x16, gate[0], up[0], gate[1], up[1], sub_e,
+                               sub_off, sub_cnt, sorted_tok, P)
+    out = ext.moe_fp8f16_down(hh, down[0], down[1], sub_e, sub_off, sub_cnt,
+                              sorted_tok, sorted_wt, N)
+    return out.to(x.dtype)
+
+
+def grouped_expert_mlp_fp8(x, gate, up, down, weights, indices):
+    """FP8 block-quantized stacked experts: gate/up/down are
+    (w8, weight_scale_inv) pairs with stacked [E, ...] layout."""
+    if _use_hip(x):
+        _require_ext("grouped_expert_mlp_fp8")
+        E = gate[0].shape[0]
+        if indices.numel() >= _MOE_GEMM_MIN_N:
+            return _moe_prefill_gemm(
+                x, None, None, None, weights, indices,
+                dequant_all=lambda: tuple(
+                    t.to(x.dtype) for t in expert_dequant_fp8(gate, up, down)))
+        sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt, _ = \
+            make_expert_subranges(indices, weights, E, max_tok=16)
+        return grouped_expert_mlp_fp8_subs(
+            x, gate, up, down,
+            (sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt))
+    return ref.grouped_expert_mlp_fp8(x, gate, up, down, weights, indices)
+
+
 # Sampling runs on [B, V] once per token — torch argmax/multinomial are
 # library kernels; fine on both devices.
 
@@ -710,3 +831,4 @@ rope_cos_sin = ref.rope_cos_sin
 yarn_mscale = ref.yarn_mscale
 dequantize = ref.dequantize
 quantize = ref.quantize
+quantize_fp8_block = ref.quantize_fp8_block

@@ -92,6 +92,18 @@ void launch_w4f16_gemv(const void*, const void*, const void*, const void*,
                        void*, float*, int, int, int, int, int, int,
                        hipStream_t);
 int w4f16_gemv_nsplit(int, int, int);
+void launch_fp8_block_dequant(const void*, const float*, void*, long, int, int,
+                              hipStream_t);
+void launch_fp8f16_gemv(const void*, const void*, const float*, void*, float*,
+                        int, int, int, int, hipStream_t);
+int fp8f16_gemv_nsplit(int, int, int);
+void launch_moe_fp8f16_gateup(const void*, const void*, const void*,
+                              const float*, const float*, void*, const int*,
+                              const int*, const int*, const int*, int, int,
+                              int, float*, long, hipStream_t);
+void launch_moe_fp8f16_down(const void*, const void*, const float*, float*,
+                            const int*, const int*, const int*, const int*,
+                            const float*, int, int, int, hipStream_t);
 void launch_gemm_kseg(const void*, const void*, void*, void*, int, int, int,
                       int, hipStream_t);
 void launch_gemm_kseg_w4(const void*, const void*, const void*, const void*,
@@ -867,6 +879,184 @@ torch::Tensor w4f16_gemv(torch::Tensor x, torch::Tensor wq,
   return y;
 }
 
+// ---- FP8 block-quantized weights (fp8_block.hip) -------------------------
+// w: float8_e4m3fn [.., O, K] contiguous; sc (weight_scale_inv): fp32
+// [.., ceil(O/128), ceil(K/128)] contiguous, one scale per 128x128 block.
+void check_fp8_block(const torch::Tensor& w, const torch::Tensor& sc,
+                     int dims, bool k128, const char* op) {
+  TORCH_CHECK(w.is_cuda() && sc.is_cuda(), op, ": tensors must be on GPU");
+  TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn, op,
+              ": weight must be float8_e4m3fn");
+  TORCH_CHECK(sc.scalar_type() == torch::kFloat32, op,
+              ": weight_scale_inv must be fp32");
+  TORCH_CHECK(w.dim() == dims && sc.dim() == dims, op, ": weight and "
+              "weight_scale_inv must be ", dims, "-d");
+  TORCH_CHECK(w.is_contiguous() && sc.is_contiguous(), op,
+              ": weight and weight_scale_inv must be contiguous");
+  const int64_t O = w.size(dims - 2), K = w.size(dims - 1);
+  TORCH_CHECK(O >= 1 && K >= 1, op, ": empty weight");
+  TORCH_CHECK(!k128 || K % 128 == 0, op, " needs K % 128 == 0 (got K=", K,
+              ")");
+  TORCH_CHECK(sc.size(dims - 2) == (O + 127) / 128 &&
+                  sc.size(dims - 1) == (K + 127) / 128 &&
+                  (dims == 2 || sc.size(0) == w.size(0)),
+              op, ": weight_scale_inv must be [.., ceil(O/128), ceil(K/128)]"
+              " (O=", O, ", K=", K, ")");
+}
+
+// [O, K] or [E, O, K] fp8 + block scales -> bf16, any O and K.
+torch::Tensor fp8_block_dequant(torch::Tensor w, torch::Tensor sc) {
+  TORCH_CHECK(w.dim() == 2 || w.dim() == 3,
+              "fp8_block_dequant: weight must be [O, K] or [E, O, K]");
+  check_fp8_block(w, sc, (int)w.dim(), false, "fp8_block_dequant");
+  const int d = (int)w.dim();
+  const long E = d == 3 ? w.size(0) : 1;
+  const int O = w.size(d - 2), K = w.size(d - 1);
+  auto out = torch::empty(w.sizes(), w.options().dtype(torch::kBFloat16));
+  launch_fp8_block_dequant(w.data_ptr(), sc.data_ptr<float>(),
+                           out.data_ptr(), E * O, O, K, cur_stream());
+  return out;
+}
+
+// x [M, K] fp16 (M <= 64), w [O, K] fp8, sc fp32 block scales -> bf16 [M, O]
+torch::Tensor fp8f16_gemv(torch::Tensor x, torch::Tensor w, torch::Tensor sc) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kHalf && x.dim() == 2,
+              "fp8f16_gemv: x must be fp16 [M, K] on GPU");
+  check_fp8_block(w, sc, 2, true, "fp8f16_gemv");
+  auto xc = x.contiguous();
+  const int M = xc.size(0), K = xc.size(1);
+  const int O = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "fp8f16_gemv: x/weight K mismatch");
+  TORCH_CHECK(M >= 1 && M <= 64, "fp8f16_gemv needs 1 <= M <= 64 (got ", M,
+              ")");
+  auto y = torch::empty({M, O}, xc.options().dtype(torch::kBFloat16));
+  const int nk = fp8f16_gemv_nsplit(M, O, K);
+  auto yf = splitk_scratch(nk, M, O, xc.options());
+  launch_fp8f16_gemv(xc.data_ptr(), w.data_ptr(), sc.data_ptr<float>(),
+                     y.data_ptr(), f32_or_null(yf), nk, M, O, K,
+                     cur_stream());
+  return y;
+}
+
+void check_subranges(const torch::Tensor& sub_expert,
+                     const torch::Tensor& sub_off,
+                     const torch::Tensor& sub_cnt,
+                     const torch::Tensor& sorted_tok, const char* op) {
+  TORCH_CHECK(sub_expert.scalar_type() == torch::kInt32 &&
+                  sub_off.scalar_type() == torch::kInt32 &&
+                  sub_cnt.scalar_type() == torch::kInt32 &&
+                  sorted_tok.scalar_type() == torch::kInt32,
+              op, ": sub-range arrays must be int32");
+  TORCH_CHECK(sub_expert.is_contiguous() && sub_off.is_contiguous() &&
+                  sub_cnt.is_contiguous() && sorted_tok.is_contiguous(),
+              op, ": sub-range arrays must be contiguous");
+  TORCH_CHECK(sub_expert.size(0) >= 1 &&
+                  sub_off.size(0) == sub_expert.size(0) &&
+                  sub_cnt.size(0) == sub_expert.size(0),
+              op, ": sub-range arrays must have one length >= 1");
+}
+
+// Fused gate+up+SiLU over fp8 experts.  x [N, H] fp16; gw/uw [E, I, H]
+// fp8; gsc/usc [E, ceil(I/128), H/128] fp32.  clear: optional fp32 buffer
+// the launch zeroes (the down kernel's accumulator).  Returns h [P, I] fp16.
+torch::Tensor moe_fp8f16_gateup_impl(torch::Tensor x, torch::Tensor gw,
+                                     torch::Tensor uw, torch::Tensor gsc,
+                                     torch::Tensor usc,
+                                     torch::Tensor sub_expert,
+                                     torch::Tensor sub_off,
+                                     torch::Tensor sub_cnt,
+                                     torch::Tensor sorted_tok, int64_t P,
+                                     const torch::Tensor& clear) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kHalf && x.dim() == 2,
+              "moe_fp8f16_gateup: x must be fp16 [N, H] on GPU");
+  check_fp8_block(gw, gsc, 3, true, "moe_fp8f16_gateup");
+  check_fp8_block(uw, usc, 3, true, "moe_fp8f16_gateup");
+  check_subranges(sub_expert, sub_off, sub_cnt, sorted_tok,
+                  "moe_fp8f16_gateup");
+  TORCH_CHECK(gw.sizes() == uw.sizes(), "gate/up shape mismatch");
+  const int H = x.size(1);
+  const int I = gw.size(1);
+  const int S = sub_expert.size(0);
+  TORCH_CHECK(gw.size(2) == H, "moe_fp8f16_gateup: x/weight H mismatch");
+  TORCH_CHECK(P == sorted_tok.size(0), "P must be len(sorted_tok)");
+  auto h = torch::empty({P, I}, x.options());
+  launch_moe_fp8f16_gateup(
+      x.contiguous().data_ptr(), gw.data_ptr(), uw.data_ptr(),
+      gsc.data_ptr<float>(), usc.data_ptr<float>(), h.data_ptr(),
+      sub_expert.data_ptr<int>(), sub_off.data_ptr<int>(),
+      sub_cnt.data_ptr<int>(), sorted_tok.data_ptr<int>(), S, H, I,
+      clear.defined() ? clear.data_ptr<float>() : nullptr,
+      clear.defined() ? clear.numel() : 0, cur_stream());
+  return h;
+}
+
+torch::Tensor moe_fp8f16_gateup(torch::Tensor x, torch::Tensor gw,
+                                torch::Tensor uw, torch::Tensor gsc,
+                                torch::Tensor usc, torch::Tensor sub_expert,
+                                torch::Tensor sub_off, torch::Tensor sub_cnt,
+                                torch::Tensor sorted_tok, int64_t P) {
+  return moe_fp8f16_gateup_impl(x, gw, uw, gsc, usc, sub_expert, sub_off,
+                                sub_cnt, sorted_tok, P, torch::Tensor());
+}
+
+// gate+up that also hands moe_fp8f16_down its accumulator (fp32 [N, Hout],
+// allocated uninitialised, zeroed by the gate+up launch).  Returns (h, acc).
+std::vector<torch::Tensor> moe_fp8f16_gateup_acc(
+    torch::Tensor x, torch::Tensor gw, torch::Tensor uw, torch::Tensor gsc,
+    torch::Tensor usc, torch::Tensor sub_expert, torch::Tensor sub_off,
+    torch::Tensor sub_cnt, torch::Tensor sorted_tok, int64_t P, int64_t N,
+    int64_t Hout) {
+  TORCH_CHECK(N >= 1 && Hout >= 1, "accumulator shape must be positive");
+  auto acc = torch::empty({N, Hout}, x.options().dtype(torch::kFloat32));
+  auto h = moe_fp8f16_gateup_impl(x, gw, uw, gsc, usc, sub_expert, sub_off,
+                                  sub_cnt, sorted_tok, P, acc);
+  return {h, acc};
+}
+
+// hh [P, I] fp16; dw [E, H, I] fp8; dsc [E, ceil(H/128), I/128] fp32.
+// acc: the fp32 [N, H] accumulator a preceding moe_fp8f16_gateup_acc
+// zeroed on this stream; without it the binding zero-fills its own.
+torch::Tensor moe_fp8f16_down(torch::Tensor hh, torch::Tensor dw,
+                              torch::Tensor dsc, torch::Tensor sub_expert,
+                              torch::Tensor sub_off, torch::Tensor sub_cnt,
+                              torch::Tensor sorted_tok,
+                              torch::Tensor sorted_wt, int64_t N,
+                              c10::optional<torch::Tensor> acc) {
+  TORCH_CHECK(hh.is_cuda() && hh.scalar_type() == torch::kHalf &&
+                  hh.dim() == 2,
+              "moe_fp8f16_down: h must be fp16 [P, I] on GPU");
+  check_fp8_block(dw, dsc, 3, true, "moe_fp8f16_down");
+  check_subranges(sub_expert, sub_off, sub_cnt, sorted_tok,
+                  "moe_fp8f16_down");
+  TORCH_CHECK(sorted_wt.scalar_type() == torch::kFloat32 &&
+                  sorted_wt.is_contiguous() &&
+                  sorted_wt.size(0) == sorted_tok.size(0) &&
+                  hh.size(0) == sorted_tok.size(0),
+              "moe_fp8f16_down: sorted_wt fp32 and h rows must match "
+              "sorted_tok");
+  const int I = hh.size(1);
+  const int H = dw.size(1);
+  const int S = sub_expert.size(0);
+  TORCH_CHECK(dw.size(2) == I, "moe_fp8f16_down: h/weight I mismatch");
+  torch::Tensor out;
+  if (acc.has_value()) {
+    out = *acc;
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kFloat32 &&
+                    out.is_contiguous() && out.dim() == 2 &&
+                    out.size(0) == N && out.size(1) == H,
+                "acc must be contiguous fp32 [N, H]");
+  } else {
+    out = torch::zeros({N, H}, hh.options().dtype(torch::kFloat32));
+  }
+  launch_moe_fp8f16_down(
+      hh.contiguous().data_ptr(), dw.data_ptr(), dsc.data_ptr<float>(),
+      out.data_ptr<float>(), sub_expert.data_ptr<int>(),
+      sub_off.data_ptr<int>(), sub_cnt.data_ptr<int>(),
+      sorted_tok.data_ptr<int>(), sorted_wt.data_ptr<float>(), S, I, H,
+      cur_stream());
+  return out;
+}
+
 std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
                                               int64_t s_upper, int64_t max_tok,
                                               double routed_scaling,
@@ -997,6 +1187,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("sub_cnt"), pybind11::arg("sorted_tok"),
         pybind11::arg("sorted_wt"), pybind11::arg("N"), pybind11::arg("gs"),
         pybind11::arg("bits"), pybind11::arg("acc") = pybind11::none());
+  m.def("fp8_block_dequant", &fp8_block_dequant);
+  m.def("fp8f16_gemv", &fp8f16_gemv);
+  m.def("fp8f16_gemv_nsplit", [](int64_t M, int64_t O, int64_t K) {
+    return fp8f16_gemv_nsplit((int)M, (int)O, (int)K);
+  });
+  m.def("moe_fp8f16_gateup", &moe_fp8f16_gateup);
+  m.def("moe_fp8f16_gateup_acc", &moe_fp8f16_gateup_acc);
+  m.def("moe_fp8f16_down", &moe_fp8f16_down, pybind11::arg("hh"),
+        pybind11::arg("dw"), pybind11::arg("dsc"),
+        pybind11::arg("sub_expert"), pybind11::arg("sub_off"),
+        pybind11::arg("sub_cnt"), pybind11::arg("sorted_tok"),
+        pybind11::arg("sorted_wt"), pybind11::arg("N"),
+        pybind11::arg("acc") = pybind11::none());
   m.def("moe_gate_subranges", &moe_gate_subranges, pybind11::arg("logits"),
         pybind11::arg("top_k"), pybind11::arg("s_upper"),
         pybind11::arg("max_tok"), pybind11::arg("routed_scaling"),

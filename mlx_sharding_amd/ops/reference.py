@@ -248,6 +248,69 @@ def quantized_linear(x: torch.Tensor, w_q: torch.Tensor, scales: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# FP8 block-quantized linear (DeepSeek-V3/R1 checkpoints, W8A16)
+# ---------------------------------------------------------------------------
+
+FP8_BLOCK = 128
+FP8_MAX = 448.0  # largest finite float8_e4m3fn
+
+
+def _expand_block_scale(scale_inv: torch.Tensor, O: int, K: int) -> torch.Tensor:
+    """[.., ceil(O/128), ceil(K/128)] block scales -> fp32 [.., O, K]."""
+    s = scale_inv.float().repeat_interleave(FP8_BLOCK, dim=-2)
+    s = s.repeat_interleave(FP8_BLOCK, dim=-1)
+    return s[..., :O, :K]
+
+
+def dequantize_fp8_block(w8: torch.Tensor, scale_inv: torch.Tensor) -> torch.Tensor:
+    """W[o, k] = float(w8[o, k]) * scale_inv[o // 128, k // 128], fp32.
+
+    w8: float8_e4m3fn [O, K] or stacked [E, O, K]; scale_inv: fp32
+    [.., ceil(O/128), ceil(K/128)] (partial last blocks in both
+    dimensions)."""
+    O, K = w8.shape[-2], w8.shape[-1]
+    rb, kb = -(-O // FP8_BLOCK), -(-K // FP8_BLOCK)
+    if (scale_inv.dim() != w8.dim() or scale_inv.shape[-2:] != (rb, kb)
+            or scale_inv.shape[:-2] != w8.shape[:-2]):
+        raise ValueError(
+            f"dequantize_fp8_block: weight_scale_inv shape "
+            f"{tuple(scale_inv.shape)} does not match weight "
+            f"{tuple(w8.shape)} in 128x128 blocks")
+    return w8.float() * _expand_block_scale(scale_inv, O, K)
+
+
+def quantize_fp8_block(w: torch.Tensor):
+    """Per 128x128 block: scale_inv = amax / 448 (1 for an all-zero
+    block), w8 = (w / scale_inv) as float8_e4m3fn.  w: [O, K] or
+    [E, O, K].  Returns (w8, scale_inv fp32)."""
+    O, K = w.shape[-2], w.shape[-1]
+    rb, kb = -(-O // FP8_BLOCK), -(-K // FP8_BLOCK)
+    wf = w.float()
+    pad = F.pad(wf.abs(), (0, kb * FP8_BLOCK - K, 0, rb * FP8_BLOCK - O))
+    amax = pad.reshape(*w.shape[:-2], rb, FP8_BLOCK, kb, FP8_BLOCK) \
+        .amax(dim=(-3, -1))
+    scale_inv = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    w8 = (wf / _expand_block_scale(scale_inv, O, K)).to(torch.float8_e4m3fn)
+    return w8, scale_inv
+
+
+def fp8_block_linear(x: torch.Tensor, w8: torch.Tensor,
+                     scale_inv: torch.Tensor) -> torch.Tensor:
+    """y = x @ dequant(W)^T — the dense reference path on the dequantized
+    weight."""
+    w = dequantize_fp8_block(w8, scale_inv)
+    return F.linear(x, w.to(x.dtype))
+
+
+def grouped_expert_mlp_fp8(x, gate, up, down, weights, indices):
+    """gate/up/down: (w8 [E, ., .], scale_inv) pairs; dequantize, then the
+    dense grouped reference."""
+    return grouped_expert_mlp(x, dequantize_fp8_block(*gate),
+                              dequantize_fp8_block(*up),
+                              dequantize_fp8_block(*down), weights, indices)
+
+
+# ---------------------------------------------------------------------------
 # MoE (DeepSeek-V2 group-limited greedy top-k)
 # ---------------------------------------------------------------------------
 

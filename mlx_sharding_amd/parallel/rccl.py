@@ -324,7 +324,14 @@ def build_stage_model(config: ModelConfig, rank: int, world: int,
         model = cls(config, config.shard(s, e), quant_for=quant_for)
     with torch.no_grad():
         for name, p in model.named_parameters():
-            if p.is_floating_point():
+            if p.dtype == torch.float8_e4m3fn:
+                # FP8 block weights: codes ~ N(0, 64) under a block scale
+                # of 0.02 / 64 dequantize to the dense init's N(0, 0.02)
+                p.data.copy_((torch.randn(p.shape, device=p.device) * 64.0)
+                             .clamp_(-448.0, 448.0).to(p.dtype))
+            elif name.endswith(".weight_scale_inv"):
+                p.data.fill_(0.02 / 64.0)
+            elif p.is_floating_point():
                 if name.endswith(".scales"):
                     # dequant w = s*q + b with q ~ U[0, 2^bits): match the
                     # dense init's std (0.02) so synthetic quant models

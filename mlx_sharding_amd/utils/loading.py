@@ -19,7 +19,7 @@ from typing import Dict, Optional, Tuple
 import torch
 from safetensors.torch import load_file, save_file
 
-from ..config import ModelConfig, QuantConfig
+from ..config import FP8_QUANTIZATION_CONFIG, ModelConfig, QuantConfig
 from ..models import get_model_class
 from ..models.base import StageModel
 
@@ -77,11 +77,13 @@ def make_quant_predicate(config: ModelConfig, weights: Dict[str, torch.Tensor]):
 
     A module is quantized iff the checkpoint carries a `{prefix}.scales`
     tensor — the reference's class_predicate
-    (/root/reference/shard/utils.py:54-65)."""
+    (/root/reference/shard/utils.py:54-65).  Under the fp8_block format
+    the marker is `{prefix}.weight_scale_inv` instead."""
     qc = config.quantization
     if qc is None:
         return lambda prefix: None
-    scale_prefixes = {k[: -len(".scales")] for k in weights if k.endswith(".scales")}
+    suffix = ".weight_scale_inv" if qc.fmt == "fp8_block" else ".scales"
+    scale_prefixes = {k[: -len(suffix)] for k in weights if k.endswith(suffix)}
     # stacked expert weights sanitize to switch_mlp.*; map their per-expert form too
     extra = set()
     for p in scale_prefixes:
@@ -101,15 +103,45 @@ _NO_QUANT_KEYS = ("embed_tokens", "norm", "layernorm", "gate.weight",
                   "rotary", "inv_freq")
 
 
+def _is_fp8(t: torch.Tensor) -> bool:
+    return t.is_floating_point() and t.element_size() == 1
+
+
 def quantize_weights(weights: Dict[str, torch.Tensor], config: ModelConfig,
-                     group_size: int = 64, bits: int = 4) -> None:
+                     group_size: int = 64, bits: int = 4,
+                     fmt: str = "affine") -> None:
     """Quantize a bf16/fp16 checkpoint's linear weights IN PLACE to the
     MLX affine triplet layout (weight packed uint32 + scales + biases) —
     so any dense checkpoint can run the int4/int8 path, which on this
     hardware is the FAST path (docs/PERFORMANCE.md).  Embeddings, norms
     and tiny router gates stay dense (mirrors what MLX's nn.quantize
-    covers for these models).  Sets config's quantization stanza."""
+    covers for these models).  Sets config's quantization stanza.
+
+    fmt="fp8" writes the FP8 block layout instead (float8_e4m3fn weight
+    + fp32 weight_scale_inv per 128x128 block, the `quantization_config`
+    stanza of the DeepSeek-V3 checkpoints) over the same key filter;
+    group_size and bits are ignored."""
     from ..ops import reference as ref
+    if fmt not in ("affine", "fp8"):
+        raise ValueError(f"quantize_weights: unknown fmt {fmt!r}")
+    if (any(_is_fp8(w) for w in weights.values())
+            or (config.raw.get("quantization_config") or {})
+            .get("quant_method") == "fp8"):
+        raise ValueError(
+            "quantize_weights: the checkpoint is already FP8 "
+            "block-quantized; load it without a quantize request")
+    if fmt == "fp8":
+        for k in list(weights.keys()):
+            w = weights[k]
+            if (not k.endswith(".weight") or w.dim() not in (2, 3)
+                    or not w.is_floating_point()
+                    or any(tag in k for tag in _NO_QUANT_KEYS)):
+                continue
+            w8, sinv = ref.quantize_fp8_block(w)
+            weights[k] = w8
+            weights[k[:-len(".weight")] + ".weight_scale_inv"] = sinv
+        config.raw["quantization_config"] = dict(FP8_QUANTIZATION_CONFIG)
+        return
     for k in list(weights.keys()):
         w = weights[k]
         if (not k.endswith(".weight") or w.dim() not in (2, 3)
@@ -136,7 +168,7 @@ def load_model(model_path: str | Path,
                end_layer: Optional[int] = None,
                device: str = "cpu",
                dtype: Optional[torch.dtype] = None,
-               quantize: Optional[Tuple[int, int]] = None) -> Tuple[StageModel, ModelConfig]:
+               quantize=None) -> Tuple[StageModel, ModelConfig]:
     """Load one pipeline stage from a checkpoint directory.
 
     Works with both pre-sharded checkpoints (config.json carries
@@ -145,14 +177,24 @@ def load_model(model_path: str | Path,
     ``model_path`` may be a local directory or a HF hub repo id
     (resolved via the snapshot cache, reference utils.py:33-39).
     ``quantize=(bits, group_size)`` converts a dense checkpoint to the
-    w4a16/w8a16 layout at load (quantize_weights)."""
+    w4a16/w8a16 layout at load (quantize_weights); ``quantize="fp8"`` to
+    the FP8 block layout.  Asking to quantize an FP8 checkpoint is a
+    ValueError."""
     model_path = get_model_path(model_path)
     config = ModelConfig.load(model_path)
     shard = config.shard(start_layer, end_layer)
     weights = load_weights(model_path)
-    if quantize is not None and config.quantization is None:
-        bits, gs = quantize
-        quantize_weights(weights, config, group_size=gs, bits=bits)
+    qc0 = config.quantization
+    if quantize is not None and qc0 is not None and qc0.fmt == "fp8_block":
+        raise ValueError(
+            "load_model: the checkpoint is already FP8 block-quantized; "
+            "drop the quantize request")
+    if quantize is not None and qc0 is None:
+        if quantize == "fp8":
+            quantize_weights(weights, config, fmt="fp8")
+        else:
+            bits, gs = quantize
+            quantize_weights(weights, config, group_size=gs, bits=bits)
     cls = get_model_class(config.model_type)
     quant_for = make_quant_predicate(config, weights)
     model = cls(config, shard, quant_for=quant_for)
@@ -160,9 +202,22 @@ def load_model(model_path: str | Path,
         for k in list(weights):
             # the V3 router's selection bias stays fp32 whatever the model
             # dtype (rounding it can change which experts are picked)
+            # FP8 weights and their fp32 block scales keep their dtypes too
             if (weights[k].is_floating_point()
-                    and not k.endswith("e_score_correction_bias")):
+                    and not _is_fp8(weights[k])
+                    and not k.endswith(("e_score_correction_bias",
+                                        ".weight_scale_inv"))):
                 weights[k] = weights[k].to(dtype)
+        # the modules are built in bf16 and load_state_dict copies INTO
+        # them: give the same parameters the requested dtype first, or a
+        # float32 load would be rounded to bf16 on the way in (affine
+        # scales/biases stay bf16: the packed kernels read them as such)
+        for name, p in model.named_parameters():
+            if (p.is_floating_point() and not _is_fp8(p)
+                    and not name.endswith(("e_score_correction_bias",
+                                           ".weight_scale_inv",
+                                           ".scales", ".biases"))):
+                p.data = p.data.to(dtype)
     model.load_weights(weights)
     model.to(device)
     model.eval()

@@ -4,7 +4,7 @@ configs of the models BASELINE.json names."""
 
 from __future__ import annotations
 
-from ..config import ModelConfig
+from ..config import FP8_QUANTIZATION_CONFIG, ModelConfig
 
 PRESETS = {
     # headline model: DeepSeek-Coder-V2-Lite-Instruct (15.7B total, 2.4B active)
@@ -242,9 +242,25 @@ PRESETS["debug-deepseek-v3"] = dict(
 )
 
 
+# debug-deepseek-v3 with every routed-expert GEMM on K % 128 == 0 (hidden
+# 256, expert inner 128) — the shapes the FP8 block kernels serve
+PRESETS["debug-deepseek-v3-fp8"] = dict(
+    PRESETS["debug-deepseek-v3"],
+    hidden_size=256,
+    moe_intermediate_size=128,
+)
+
+
 def get_preset(name: str, quant: bool = False,
-               group_size: int = 64, bits: int = 4) -> ModelConfig:
+               group_size: int = 64, bits: int = 4,
+               fp8: bool = False) -> ModelConfig:
+    """fp8=True adds the FP8 block `quantization_config` stanza (128x128
+    e4m3 blocks) instead of an affine `quantization` one."""
     raw = dict(PRESETS[name])
+    if quant and fp8:
+        raise ValueError("get_preset: quant and fp8 are exclusive")
     if quant:
         raw["quantization"] = {"group_size": group_size, "bits": bits}
+    if fp8:
+        raw["quantization_config"] = dict(FP8_QUANTIZATION_CONFIG)
     return ModelConfig.from_dict(raw)

@@ -96,9 +96,96 @@ def bench_v3(ops, ext, dev="cuda"):
               f"~{kv_bytes / (med / 1e6) / 1e12:.2f} TB/s of one K pass")
 
 
+def bench_fp8(ops, ext, dev="cuda", E=64, windows=3):
+    """FP8 block-quantized kernels against the 8-bit affine (gs 128)
+    fp16-dequant kernels, which stream the same weight bytes: DeepSeek-V3
+    decode shapes (H=7168, I=2048, 64 tokens x top-8 over E experts) and
+    an o_proj-class GEMV.  Same process, alternating, `windows` timed
+    windows each; prints median and min-max us and achieved weight
+    bytes/s."""
+    H, I, N, K = 7168, 2048, 64, 8
+    g = torch.Generator(device=dev).manual_seed(3)
+
+    def rand8(*shape):
+        return (torch.randn(*shape, device=dev, generator=g) * 64.0) \
+            .clamp_(-448, 448).to(torch.float8_e4m3fn)
+
+    def randq(*shape):
+        return torch.randint(0, 2 ** 31 - 1, shape, device=dev,
+                             dtype=torch.int32, generator=g)
+
+    def sb(*shape):
+        return torch.rand(*shape, device=dev, generator=g) \
+            .to(torch.bfloat16) * 0.01
+
+    logits = torch.randn(N, E, device=dev, generator=g).to(torch.bfloat16)
+    subs = ops.moe_gate_subranges(logits, K, max_tok=16)
+    s_e, s_off, s_cnt, s_tok, s_wt = subs
+    P = N * K
+    x16 = (torch.randn(N, H, device=dev, generator=g) * 0.1).to(torch.float16)
+    hh = (torch.randn(P, I, device=dev, generator=g) * 0.1).to(torch.float16)
+    active = int((torch.bincount(s_e[s_cnt > 0].long(), minlength=E) > 0).sum())
+
+    # fp8 operands
+    g8, u8, d8 = rand8(E, I, H), rand8(E, I, H), rand8(E, H, I)
+    gs8 = torch.full((E, I // 128, H // 128), 3e-4, device=dev)
+    ds8 = torch.full((E, H // 128, I // 128), 3e-4, device=dev)
+    # 8-bit affine operands, group size 128 (repacked once)
+    gq, uq, dq = (ops.repack_w4(randq(E, I, H // 4), 8),
+                  ops.repack_w4(randq(E, I, H // 4), 8),
+                  ops.repack_w4(randq(E, H, I // 4), 8))
+    gsc, gbi = sb(E, I, H // 128), sb(E, I, H // 128)
+    dsc, dbi = sb(E, H, I // 128), sb(E, H, I // 128)
+
+    cases = {
+        "gateup": (
+            lambda: ext.moe_fp8f16_gateup(x16, g8, u8, gs8, gs8, s_e, s_off,
+                                          s_cnt, s_tok, P),
+            lambda: ext.moe_w4f16_gateup(x16, gq, uq, gsc, gbi, gsc, gbi, s_e,
+                                         s_off, s_cnt, s_tok, P, 128, 8),
+            active * 2 * I * H),
+        "down": (
+            lambda: ext.moe_fp8f16_down(hh, d8, ds8, s_e, s_off, s_cnt, s_tok,
+                                        s_wt, N),
+            lambda: ext.moe_w4f16_down(hh, dq, dsc, dbi, s_e, s_off, s_cnt,
+                                       s_tok, s_wt, N, 128, 8),
+            active * H * I),
+    }
+    O, KK = 7168, 16384  # o_proj of a 128-head V3 layer
+    w8, ws = rand8(O, KK), torch.full((O // 128, KK // 128), 3e-4, device=dev)
+    wq = ops.repack_w4(randq(O, KK // 4), 8)
+    wsc, wbi = sb(O, KK // 128), sb(O, KK // 128)
+    xg = (torch.randn(N, KK, device=dev, generator=g) * 0.1).to(torch.float16)
+    cases["gemv o_proj M=64"] = (
+        lambda: ext.fp8f16_gemv(xg, w8, ws),
+        lambda: ext.w4f16_gemv(xg, wq, wsc, wbi, 128, 8), O * KK)
+    x1 = xg[:1].contiguous()
+    cases["gemv o_proj M=1"] = (
+        lambda: ext.fp8f16_gemv(x1, w8, ws),
+        lambda: ext.w4f16_gemv(x1, wq, wsc, wbi, 128, 8), O * KK)
+
+    print(f"fp8 vs w8-affine(gs128): H={H} I={I} N={N} top-{K} E={E} "
+          f"({active} experts active)")
+    for name, (f8, w8a, nbytes) in cases.items():
+        ts = {"fp8": [], "w8": []}
+        for _ in range(windows):  # alternate the two paths
+            ts["fp8"].append(timeit(f8, 30, warmup=5))
+            ts["w8"].append(timeit(w8a, 30, warmup=5))
+        for k, v in ts.items():
+            v.sort()
+            med = v[len(v) // 2]
+            print(f"  {name:18s} {k:4s} median {med:8.1f} us  "
+                  f"min {v[0]:8.1f}  max {v[-1]:8.1f}  "
+                  f"{nbytes / (med / 1e6) / 1e12:5.2f} TB/s "
+                  f"({nbytes / (v[-1] / 1e6) / 1e12:.2f}-"
+                  f"{nbytes / (v[0] / 1e6) / 1e12:.2f})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--fp8-only", action="store_true",
+                    help="only the FP8-block vs 8-bit-affine comparison")
     ap.add_argument("--gate-only", action="store_true",
                     help="only the grouped-gating fused-vs-torch line")
     ap.add_argument("--v3-only", action="store_true",
@@ -117,6 +204,9 @@ def main():
         return
     if args.v3_only:
         bench_v3(ops, ext, dev)
+        return
+    if args.fp8_only:
+        bench_fp8(ops, ext, dev)
         return
 
     E, H, I, N, K = 64, 2048, 1408, 64, 6

@@ -15,7 +15,17 @@ from mlx_sharding_amd.utils.presets import get_preset
 
 name = sys.argv[1] if len(sys.argv) > 1 else "deepseek-v2-lite"
 n_tok = int(sys.argv[2]) if len(sys.argv) > 2 else 200
-config = get_preset(name, quant="deepseek" in name)
+# optional third argument: int4 (the default for deepseek presets), w8
+# (8-bit affine, gs 128), fp8 (FP8 128x128 blocks) or bf16
+mode = sys.argv[3] if len(sys.argv) > 3 else \
+    ("int4" if "deepseek" in name else "bf16")
+if mode == "fp8":
+    config = get_preset(name, fp8=True)
+elif mode == "w8":
+    config = get_preset(name, quant=True, group_size=128, bits=8)
+else:
+    config = get_preset(name, quant=mode == "int4")
+name = f"{name} [{mode}]"
 qc = config.quantization
 dev = torch.device("cuda", 0)
 model = build_stage_model(config, 0, 1, dev,
