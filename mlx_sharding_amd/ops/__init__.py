@@ -799,13 +799,74 @@ def grouped_expert_mlp_fp8_subs(x, gate, up, down, subs, raw: bool = False):
     return out.to(x.dtype)
 
 
+_FP8_PREFILL_ENV = "MLXS_AMD_FP8_PREFILL"
+
+
+def _fp8_prefill_env() -> Optional[str]:
+    return os.environ.get(_FP8_PREFILL_ENV) or None
+
+
+def _fp8_prefill_route(pairs: int, resident: bool, kernel_ok: bool,
+                       env: Optional[str]) -> str:
+    """Which path a GPU grouped_expert_mlp_fp8 call takes:
+
+    "tiles16" — the 16-token packed kernels (under _MOE_GEMM_MIN_N pairs);
+    "dense"   — _moe_prefill_gemm on the dense bf16 triplet, resident in
+                the dq-cache or dequantized for this call;
+    "packed"  — the wide-tile packed kernels (fp8_prefill.hip).
+
+    resident: expert_dequant_fp8_resident has a dense triplet (only asked
+    for when env is unset).  kernel_ok: _fp8_kernel_ok holds for all three
+    matrices.  env: MLXS_AMD_FP8_PREFILL, None when unset."""
+    if env not in (None, "packed", "dense"):
+        raise ValueError("%s must be 'packed' or 'dense' (got %r)"
+                         % (_FP8_PREFILL_ENV, env))
+    if pairs < _MOE_GEMM_MIN_N:
+        return "tiles16"
+    if env == "dense" or not kernel_ok:
+        return "dense"
+    if env == "packed":
+        return "packed"
+    return "dense" if resident else "packed"
+
+
+def _moe_prefill_fp8_packed(x, gate, up, down, weights, indices):
+    """Prefill from the packed e4m3 stacks: sub-ranges of the wide
+    kernels' tile (device ops only, no host sync), fused gate+up+SiLU,
+    down with the routing-weighted fp32 scatter."""
+    ext = _require_ext("grouped_expert_mlp_fp8")
+    sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt, _ = \
+        make_expert_subranges(indices, weights, gate[0].shape[0],
+                              max_tok=ext.moe_fp8f16_wide_tile())
+    hh = ext.moe_fp8f16_gateup_wide(
+        _to_f16_cached(x), gate[0], up[0], gate[1], up[1], sub_e, sub_off,
+        sub_cnt, sorted_tok, sorted_tok.shape[0])
+    out = ext.moe_fp8f16_down_wide(hh, down[0], down[1], sub_e, sub_off,
+                                   sub_cnt, sorted_tok, sorted_wt, x.shape[0])
+    return out.to(x.dtype)
+
+
 def grouped_expert_mlp_fp8(x, gate, up, down, weights, indices):
     """FP8 block-quantized stacked experts: gate/up/down are
-    (w8, weight_scale_inv) pairs with stacked [E, ...] layout."""
+    (w8, weight_scale_inv) pairs with stacked [E, ...] layout.  On the
+    GPU the path is _fp8_prefill_route's."""
     if _use_hip(x):
         _require_ext("grouped_expert_mlp_fp8")
         E = gate[0].shape[0]
-        if indices.numel() >= _MOE_GEMM_MIN_N:
+        env = _fp8_prefill_env()
+        pairs = indices.numel()
+        kernel_ok = (_fp8_kernel_ok(*gate) and _fp8_kernel_ok(*up)
+                     and _fp8_kernel_ok(*down))
+        # the resident lookup builds the dense copy when the budget admits
+        # it: only ask where the answer decides the route
+        resident = (env is None and kernel_ok and pairs >= _MOE_GEMM_MIN_N
+                    and expert_dequant_fp8_resident(gate, up, down)
+                    is not None)
+        route = _fp8_prefill_route(pairs, resident, kernel_ok, env)
+        if route == "packed":
+            return _moe_prefill_fp8_packed(x, gate, up, down, weights,
+                                           indices)
+        if route == "dense":
             return _moe_prefill_gemm(
                 x, None, None, None, weights, indices,
                 dequant_all=lambda: tuple(

@@ -104,6 +104,15 @@ void launch_moe_fp8f16_gateup(const void*, const void*, const void*,
 void launch_moe_fp8f16_down(const void*, const void*, const float*, float*,
                             const int*, const int*, const int*, const int*,
                             const float*, int, int, int, hipStream_t);
+int moe_fp8f16_wide_tile();
+void launch_moe_fp8f16_gateup_wide(const void*, const void*, const void*,
+                                   const float*, const float*, void*,
+                                   const int*, const int*, const int*,
+                                   const int*, int, int, int, hipStream_t);
+void launch_moe_fp8f16_down_wide(const void*, const void*, const float*,
+                                 float*, const int*, const int*, const int*,
+                                 const int*, const float*, int, int, int,
+                                 hipStream_t);
 void launch_gemm_kseg(const void*, const void*, void*, void*, int, int, int,
                       int, hipStream_t);
 void launch_gemm_kseg_w4(const void*, const void*, const void*, const void*,
@@ -1057,6 +1066,73 @@ torch::Tensor moe_fp8f16_down(torch::Tensor hh, torch::Tensor dw,
   return out;
 }
 
+// The prefill-regime pair (fp8_prefill.hip): the same contract over
+// sub-ranges built for moe_fp8f16_wide_tile() tokens.
+torch::Tensor moe_fp8f16_gateup_wide(torch::Tensor x, torch::Tensor gw,
+                                     torch::Tensor uw, torch::Tensor gsc,
+                                     torch::Tensor usc,
+                                     torch::Tensor sub_expert,
+                                     torch::Tensor sub_off,
+                                     torch::Tensor sub_cnt,
+                                     torch::Tensor sorted_tok, int64_t P) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kHalf && x.dim() == 2,
+              "moe_fp8f16_gateup_wide: x must be fp16 [N, H] on GPU");
+  check_fp8_block(gw, gsc, 3, true, "moe_fp8f16_gateup_wide");
+  check_fp8_block(uw, usc, 3, true, "moe_fp8f16_gateup_wide");
+  check_subranges(sub_expert, sub_off, sub_cnt, sorted_tok,
+                  "moe_fp8f16_gateup_wide");
+  TORCH_CHECK(gw.sizes() == uw.sizes(),
+              "moe_fp8f16_gateup_wide: gate/up shape mismatch");
+  const int H = x.size(1);
+  const int I = gw.size(1);
+  const int S = sub_expert.size(0);
+  TORCH_CHECK(gw.size(2) == H, "moe_fp8f16_gateup_wide: x/weight H mismatch");
+  TORCH_CHECK(P == sorted_tok.size(0),
+              "moe_fp8f16_gateup_wide: P must be len(sorted_tok)");
+  auto h = torch::empty({P, I}, x.options());
+  launch_moe_fp8f16_gateup_wide(
+      x.contiguous().data_ptr(), gw.data_ptr(), uw.data_ptr(),
+      gsc.data_ptr<float>(), usc.data_ptr<float>(), h.data_ptr(),
+      sub_expert.data_ptr<int>(), sub_off.data_ptr<int>(),
+      sub_cnt.data_ptr<int>(), sorted_tok.data_ptr<int>(), S, H, I,
+      cur_stream());
+  return h;
+}
+
+torch::Tensor moe_fp8f16_down_wide(torch::Tensor hh, torch::Tensor dw,
+                                   torch::Tensor dsc,
+                                   torch::Tensor sub_expert,
+                                   torch::Tensor sub_off,
+                                   torch::Tensor sub_cnt,
+                                   torch::Tensor sorted_tok,
+                                   torch::Tensor sorted_wt, int64_t N) {
+  TORCH_CHECK(hh.is_cuda() && hh.scalar_type() == torch::kHalf &&
+                  hh.dim() == 2,
+              "moe_fp8f16_down_wide: h must be fp16 [P, I] on GPU");
+  check_fp8_block(dw, dsc, 3, true, "moe_fp8f16_down_wide");
+  check_subranges(sub_expert, sub_off, sub_cnt, sorted_tok,
+                  "moe_fp8f16_down_wide");
+  TORCH_CHECK(sorted_wt.scalar_type() == torch::kFloat32 &&
+                  sorted_wt.is_contiguous() &&
+                  sorted_wt.size(0) == sorted_tok.size(0) &&
+                  hh.size(0) == sorted_tok.size(0),
+              "moe_fp8f16_down_wide: sorted_wt fp32 and h rows must match "
+              "sorted_tok");
+  TORCH_CHECK(N >= 1, "moe_fp8f16_down_wide: N must be positive");
+  const int I = hh.size(1);
+  const int H = dw.size(1);
+  const int S = sub_expert.size(0);
+  TORCH_CHECK(dw.size(2) == I, "moe_fp8f16_down_wide: h/weight I mismatch");
+  auto out = torch::zeros({N, H}, hh.options().dtype(torch::kFloat32));
+  launch_moe_fp8f16_down_wide(
+      hh.contiguous().data_ptr(), dw.data_ptr(), dsc.data_ptr<float>(),
+      out.data_ptr<float>(), sub_expert.data_ptr<int>(),
+      sub_off.data_ptr<int>(), sub_cnt.data_ptr<int>(),
+      sorted_tok.data_ptr<int>(), sorted_wt.data_ptr<float>(), S, I, H,
+      cur_stream());
+  return out;
+}
+
 std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
                                               int64_t s_upper, int64_t max_tok,
                                               double routed_scaling,
@@ -1200,6 +1276,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("sub_cnt"), pybind11::arg("sorted_tok"),
         pybind11::arg("sorted_wt"), pybind11::arg("N"),
         pybind11::arg("acc") = pybind11::none());
+  m.def("moe_fp8f16_gateup_wide", &moe_fp8f16_gateup_wide);
+  m.def("moe_fp8f16_down_wide", &moe_fp8f16_down_wide);
+  m.def("moe_fp8f16_wide_tile", []() { return moe_fp8f16_wide_tile(); });
   m.def("moe_gate_subranges", &moe_gate_subranges, pybind11::arg("logits"),
         pybind11::arg("top_k"), pybind11::arg("s_upper"),
         pybind11::arg("max_tok"), pybind11::arg("routed_scaling"),

@@ -181,9 +181,111 @@ def bench_fp8(ops, ext, dev="cuda", E=64, windows=3):
                   f"{nbytes / (v[0] / 1e6) / 1e12:.2f})")
 
 
+def bench_fp8_prefill(ops, ext, dev="cuda", windows=3, iters=3):
+    """One DeepSeek-V3 MoE layer (E=256, H=7168, I=2048, top-8, seeded
+    random routing) prefilled from FP8 experts at N=4096 and N=512 tokens:
+    the packed wide-tile route against the dequant-per-call route
+    (MLXS_AMD_FP8_PREFILL=dense with the dq-cache off).  Same process,
+    alternating, `windows` timed windows of `iters` calls each after one
+    warm-up call; prints median and min-max ms and the peak-memory growth
+    of one call per route, then each wide kernel alone with its achieved
+    weight bytes/s (every activated expert's matrices counted once) and
+    FLOP/s, both computed from shapes."""
+    import os
+    E, H, I, K = 256, 7168, 2048, 8
+    TM = ext.moe_fp8f16_wide_tile()
+    g = torch.Generator(device=dev).manual_seed(3)
+
+    def rand8(*shape):
+        b = torch.randint(0, 256, shape, device=dev, dtype=torch.uint8,
+                          generator=g)
+        b[(b & 0x7F) == 0x7F] = 0x38  # no NaN codes
+        return b.view(torch.float8_e4m3fn)
+
+    def scales(*shape):
+        return torch.rand(*shape, device=dev, generator=g) * 2e-4 + 1e-4
+
+    gate = (rand8(E, I, H), scales(E, I // 128, H // 128))
+    up = (rand8(E, I, H), scales(E, I // 128, H // 128))
+    down = (rand8(E, H, I), scales(E, H // 128, I // 128))
+    env = {"packed": {"MLXS_AMD_FP8_PREFILL": "packed"},
+           "dense": {"MLXS_AMD_FP8_PREFILL": "dense",
+                     "MLXS_AMD_NO_DQ_CACHE": "1"}}
+
+    def run(route, x, w, idx):
+        for k in ("MLXS_AMD_FP8_PREFILL", "MLXS_AMD_NO_DQ_CACHE"):
+            os.environ.pop(k, None)
+        os.environ.update(env[route])
+        # a fresh tensor object: the packed route pays its fp16 cast
+        return ops.grouped_expert_mlp_fp8(x.view_as(x), gate, up, down, w, idx)
+
+    print(f"fp8 prefill, one V3 MoE layer: E={E} H={H} I={I} top-{K}, "
+          f"wide tile TM={TM}")
+    for N in (4096, 512):
+        x = (torch.randn(N, H, device=dev, generator=g) * 0.1) \
+            .to(torch.bfloat16)
+        idx = torch.rand(N, E, device=dev, generator=g).topk(K, dim=-1).indices
+        w = torch.rand(N, K, device=dev, generator=g).to(torch.bfloat16)
+        ts, mem, outs = {"packed": [], "dense": []}, {}, {}
+        for route in ts:  # warm-up, and the memory of one call
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            outs[route] = run(route, x, w, idx).float()
+            torch.cuda.synchronize()
+            mem[route] = torch.cuda.max_memory_allocated() - base
+        diff = float((outs["packed"] - outs["dense"]).abs().max())
+        scale = float(outs["dense"].abs().max())
+        for _ in range(windows):  # alternate the two routes
+            for route in ts:
+                ts[route].append(timeit(lambda: run(route, x, w, idx), iters,
+                                        warmup=0) / 1000)
+        print(f"  N={N}: max |packed - dense| {diff:.3e} at scale {scale:.3e}")
+        for route, v in ts.items():
+            v.sort()
+            print(f"  N={N:5d} {route:6s} median {v[len(v) // 2]:8.2f} ms  "
+                  f"min {v[0]:8.2f}  max {v[-1]:8.2f}  "
+                  f"peak memory +{mem[route] / 2 ** 30:6.2f} GiB")
+        # the two wide kernels alone
+        subs = ops.make_expert_subranges(idx, w, E, max_tok=TM)[:5]
+        s_e, s_off, s_cnt, s_tok, s_wt = subs
+        P = N * K
+        active = int((torch.bincount(idx.reshape(-1), minlength=E) > 0).sum())
+        tiles = int((s_cnt > 0).sum())
+        x16 = x.to(torch.float16)
+        hh = ext.moe_fp8f16_gateup_wide(x16, gate[0], up[0], gate[1], up[1],
+                                        s_e, s_off, s_cnt, s_tok, P)
+        kernels = {
+            "gateup_wide": (
+                lambda: ext.moe_fp8f16_gateup_wide(
+                    x16, gate[0], up[0], gate[1], up[1], s_e, s_off, s_cnt,
+                    s_tok, P),
+                active * 2 * I * H, 2.0 * P * 2 * I * H),
+            "down_wide": (
+                lambda: ext.moe_fp8f16_down_wide(
+                    hh, down[0], down[1], s_e, s_off, s_cnt, s_tok, s_wt, N),
+                active * H * I, 2.0 * P * H * I),
+        }
+        print(f"  N={N}: {active} experts active, {tiles} tiles of <= {TM} "
+              f"tokens")
+        for name, (fn, nbytes, flops) in kernels.items():
+            v = sorted(timeit(fn, iters, warmup=1) for _ in range(windows))
+            med = v[len(v) // 2]
+            print(f"  N={N:5d} {name:12s} median {med / 1000:8.2f} ms  "
+                  f"min {v[0] / 1000:8.2f}  max {v[-1] / 1000:8.2f}  "
+                  f"{nbytes / (med / 1e6) / 1e12:5.2f} TB/s of weights  "
+                  f"{flops / (med / 1e6) / 1e12:6.1f} TFLOP/s")
+        del x16, hh, outs
+    for k in ("MLXS_AMD_FP8_PREFILL", "MLXS_AMD_NO_DQ_CACHE"):
+        os.environ.pop(k, None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--fp8-prefill", action="store_true",
+                    help="only the FP8 MoE prefill comparison: packed "
+                         "wide-tile route vs dequant per call")
     ap.add_argument("--fp8-only", action="store_true",
                     help="only the FP8-block vs 8-bit-affine comparison")
     ap.add_argument("--gate-only", action="store_true",
@@ -207,6 +309,9 @@ def main():
         return
     if args.fp8_only:
         bench_fp8(ops, ext, dev)
+        return
+    if args.fp8_prefill:
+        bench_fp8_prefill(ops, ext, dev)
         return
 
     E, H, I, N, K = 64, 2048, 1408, 64, 6
