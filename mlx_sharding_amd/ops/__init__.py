@@ -879,11 +879,31 @@ def grouped_expert_mlp_fp8(x, gate, up, down, weights, indices):
     return ref.grouped_expert_mlp_fp8(x, gate, up, down, weights, indices)
 
 
-# Sampling runs on [B, V] once per token — torch argmax/multinomial are
-# library kernels; fine on both devices.
+# One request at a time (engine.generate_step, the B=1 serving loop and
+# seeded rows of a batch): torch argmax/multinomial are library kernels;
+# fine on both devices.
 
 def sample(logits, temperature: float = 0.0, top_p: float = 1.0, generator=None):
     return ref.sample(logits, temperature, top_p, generator)
+
+
+SAMPLE_ROWS_MAX_BIAS = 32     # logit_bias entries per row (the kernel's NB)
+SAMPLE_ROWS_MAX_WINDOW = 64   # repetition-penalty window per row (its W)
+
+
+def sample_rows(logits, temperature, top_p, u, active, ids_out, lse_out,
+                bias_idx=None, bias_val=None, pen_idx=None, penalty=None):
+    """Sample the active rows of logits[B, V] with per-row temperature /
+    top_p / uniform draw, after per-row logit_bias and repetition-penalty
+    edits: reference.sample_rows semantics, one kernel launch on GPU.
+    Edits logits in place; writes ids_out ([B] or [B, 1] int64) and
+    lse_out."""
+    if _use_hip(logits):
+        return _require_ext("sample_rows").sample_rows(
+            logits, temperature, top_p, u, active, ids_out, lse_out,
+            bias_idx, bias_val, pen_idx, penalty)
+    return ref.sample_rows(logits, temperature, top_p, u, active, ids_out,
+                           lse_out, bias_idx, bias_val, pen_idx, penalty)
 
 
 apply_repetition_penalty = ref.apply_repetition_penalty

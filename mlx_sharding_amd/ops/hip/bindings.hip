@@ -113,6 +113,10 @@ void launch_moe_fp8f16_down_wide(const void*, const void*, const float*,
                                  float*, const int*, const int*, const int*,
                                  const int*, const float*, int, int, int,
                                  hipStream_t);
+void launch_sample_rows(float*, const float*, const float*, const float*,
+                        const int*, long long*, long, float*, const int*,
+                        const float*, int, const int*, const float*, int, int,
+                        int, hipStream_t);
 void launch_gemm_kseg(const void*, const void*, void*, void*, int, int, int,
                       int, hipStream_t);
 void launch_gemm_kseg_w4(const void*, const void*, const void*, const void*,
@@ -1196,9 +1200,102 @@ std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
   return {sub_expert, sub_off, sub_cnt, sorted_tok, sorted_wt};
 }
 
+// reference.sample_rows on device: edits logits in place, writes ids_out
+// and lse_out for the active rows.  No allocation: safe under capture.
+void sample_rows(torch::Tensor logits, torch::Tensor temperature,
+                 torch::Tensor top_p, torch::Tensor u, torch::Tensor active,
+                 torch::Tensor ids_out, torch::Tensor lse_out,
+                 c10::optional<torch::Tensor> bias_idx,
+                 c10::optional<torch::Tensor> bias_val,
+                 c10::optional<torch::Tensor> pen_idx,
+                 c10::optional<torch::Tensor> penalty) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kFloat32 &&
+                  logits.dim() == 2 && logits.is_contiguous(),
+              "logits must be a contiguous 2-D fp32 tensor on GPU");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V < (1LL << 31) && B < (1LL << 31),
+              "logits must have 1 <= V < 2^31 columns");
+  auto vec = [&](const torch::Tensor& t, torch::ScalarType ty,
+                 const char* name, const char* tyname) {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device(), name,
+                " must be on the logits' GPU");
+    TORCH_CHECK(t.scalar_type() == ty, name, " must be ", tyname);
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == B && t.is_contiguous(), name,
+                " must be a contiguous vector of length B = ", B);
+  };
+  vec(temperature, torch::kFloat32, "temperature", "fp32");
+  vec(top_p, torch::kFloat32, "top_p", "fp32");
+  vec(u, torch::kFloat32, "u", "fp32");
+  vec(active, torch::kInt32, "active", "int32");
+  vec(lse_out, torch::kFloat32, "lse_out", "fp32");
+  TORCH_CHECK(ids_out.is_cuda() && ids_out.get_device() == logits.get_device(),
+              "ids_out must be on the logits' GPU");
+  TORCH_CHECK(ids_out.scalar_type() == torch::kInt64, "ids_out must be int64");
+  TORCH_CHECK((ids_out.dim() == 1 && ids_out.size(0) == B) ||
+                  (ids_out.dim() == 2 && ids_out.size(0) == B &&
+                   ids_out.size(1) == 1),
+              "ids_out must have shape [B] or [B, 1] with B = ", B);
+  const long ids_stride = B > 0 ? (long)ids_out.stride(0) : 1;
+  TORCH_CHECK(B <= 1 || ids_stride >= 1, "ids_out rows must not overlap");
+
+  auto table = [&](const torch::Tensor& t, torch::ScalarType ty,
+                   const char* name, const char* tyname, int64_t limit) {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device(), name,
+                " must be on the logits' GPU");
+    TORCH_CHECK(t.scalar_type() == ty, name, " must be ", tyname);
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == B && t.is_contiguous(), name,
+                " must be a contiguous [B, n] tensor with B = ", B);
+    TORCH_CHECK(t.size(1) <= limit, name, " holds at most ", limit,
+                " entries per row (got ", t.size(1), ")");
+  };
+  TORCH_CHECK(bias_idx.has_value() == bias_val.has_value(),
+              "bias_idx and bias_val must be given together");
+  TORCH_CHECK(pen_idx.has_value() == penalty.has_value(),
+              "pen_idx and penalty must be given together");
+  const int* bi = nullptr;
+  const float* bv = nullptr;
+  int NB = 0;
+  if (bias_idx.has_value()) {
+    table(*bias_idx, torch::kInt32, "bias_idx", "int32", 32);
+    table(*bias_val, torch::kFloat32, "bias_val", "fp32", 32);
+    TORCH_CHECK(bias_idx->size(1) == bias_val->size(1),
+                "bias_idx and bias_val must have the same shape");
+    NB = (int)bias_idx->size(1);
+    if (NB > 0) {
+      bi = bias_idx->data_ptr<int>();
+      bv = bias_val->data_ptr<float>();
+    }
+  }
+  const int* pi = nullptr;
+  const float* pv = nullptr;
+  int W = 0;
+  if (pen_idx.has_value()) {
+    table(*pen_idx, torch::kInt32, "pen_idx", "int32", 64);
+    vec(*penalty, torch::kFloat32, "penalty", "fp32");
+    W = (int)pen_idx->size(1);
+    if (W > 0) {
+      pi = pen_idx->data_ptr<int>();
+      pv = penalty->data_ptr<float>();
+    }
+  }
+  launch_sample_rows(logits.data_ptr<float>(), temperature.data_ptr<float>(),
+                     top_p.data_ptr<float>(), u.data_ptr<float>(),
+                     active.data_ptr<int>(),
+                     reinterpret_cast<long long*>(ids_out.data_ptr<int64_t>()),
+                     ids_stride, lse_out.data_ptr<float>(), bi, bv, NB, pi, pv,
+                     W, (int)B, (int)V, cur_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("sample_rows", &sample_rows, pybind11::arg("logits"),
+        pybind11::arg("temperature"), pybind11::arg("top_p"),
+        pybind11::arg("u"), pybind11::arg("active"), pybind11::arg("ids_out"),
+        pybind11::arg("lse_out"), pybind11::arg("bias_idx") = pybind11::none(),
+        pybind11::arg("bias_val") = pybind11::none(),
+        pybind11::arg("pen_idx") = pybind11::none(),
+        pybind11::arg("penalty") = pybind11::none());
   m.def("rms_norm", &rms_norm, "fused RMSNorm (gfx950)");
   m.def("rms_norm_residual", &rms_norm_residual, pybind11::arg("x"),
         pybind11::arg("resid"), pybind11::arg("w"), pybind11::arg("eps"),

@@ -447,3 +447,67 @@ def sample(logits: torch.Tensor, temperature: float = 0.0, top_p: float = 1.0,
         return top_p_sample(logits, top_p, temperature, generator)
     probs = torch.softmax(logits.float() / temperature, dim=-1)
     return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
+
+
+def nucleus_keep(p: torch.Tensor, top_p: float) -> torch.Tensor:
+    """Kept set of sample_rows' nucleus step over probabilities p[V]:
+    token i stays iff the mass of the tokens with p_j > p_i (strictly) is
+    < top_p.  A tie class stays or goes whole; the top class always
+    stays.  On tie-free rows this is top_p_sample's ``keep``."""
+    vals, inv = torch.unique(p, return_inverse=True)   # ascending classes
+    mass = torch.zeros_like(vals).index_add_(0, inv, p)
+    incl = torch.flip(torch.cumsum(torch.flip(mass, (0,)), 0), (0,))
+    keep = (incl - mass)[inv] < top_p
+    keep |= p == vals[-1]
+    return keep
+
+
+def sample_rows(logits, temperature, top_p, u, active, ids_out, lse_out,
+                bias_idx=None, bias_val=None, pen_idx=None, penalty=None):
+    """Batched sampling of the rows of logits[B, V] (fp32) with per-row
+    parameters — the specification of the HIP ``sample_rows`` kernel.
+
+    For every row b with active[b] != 0 (other rows leave logits[b],
+    ids_out[b] and lse_out[b] untouched):
+
+    1. edits, written back into logits[b]: x[k] += bias_val[b, j] for
+       every k = bias_idx[b, j] >= 0 (distinct keys, -1 pads), then, when
+       penalty[b] != 1, x[k] = x[k] / pen if x[k] > 0 else x[k] * pen
+       once per distinct token k >= 0 of pen_idx[b, :] — logit_bias then
+       apply_repetition_penalty;
+    2. lse_out[b] = logsumexp(x), at temperature 1, after the edits;
+    3. temperature[b] <= 0: ids_out[b] = argmax(x), lowest index on ties;
+    4. else p = softmax(x / temperature[b]), cut to nucleus_keep(p,
+       top_p[b]) when top_p[b] < 1;
+    5. with Z the kept mass, ids_out[b] is the smallest kept index i, in
+       vocabulary order, whose inclusive kept prefix sum exceeds
+       u[b] * Z; the last kept index if rounding leaves none.
+
+    ids_out may be [B] or [B, 1]."""
+    B = logits.shape[0]
+    ids = ids_out  # ids[b] = scalar fills a [B] element or a [B, 1] row
+    for b in range(B):
+        if int(active[b]) == 0:
+            continue
+        x = logits[b]
+        if bias_idx is not None:
+            sel = bias_idx[b] >= 0
+            x[bias_idx[b][sel].long()] += bias_val[b][sel]
+        if pen_idx is not None and float(penalty[b]) != 1.0:
+            k = torch.unique(pen_idx[b][pen_idx[b] >= 0]).long()
+            v = x[k]
+            x[k] = torch.where(v > 0, v / penalty[b], v * penalty[b])
+        lse_out[b] = torch.logsumexp(x, dim=-1)
+        t = float(temperature[b])
+        if t <= 0.0:
+            ids[b] = torch.nonzero(x == x.max()).view(-1)[0]
+            continue
+        p = torch.softmax(x / temperature[b], dim=-1)
+        keep = torch.ones_like(p, dtype=torch.bool)
+        if float(top_p[b]) < 1.0:
+            keep = nucleus_keep(p, float(top_p[b]))
+        kept = torch.where(keep, p, torch.zeros_like(p))
+        cdf = torch.cumsum(kept, 0)
+        hit = keep & (cdf > u[b] * cdf[-1])
+        idx = torch.nonzero(hit if bool(hit.any()) else keep).view(-1)
+        ids[b] = idx[0] if bool(hit.any()) else idx[-1]

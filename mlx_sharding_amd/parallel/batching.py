@@ -55,6 +55,44 @@ def serve_capacity() -> int:
     return int(os.environ.get("MLXS_AMD_SERVE_CAPACITY", "4096"))
 
 
+def plain_greedy(params: SamplingParams) -> bool:
+    """Argmax of the unedited logits: such rows share one batched
+    on-device argmax."""
+    return (params.temperature <= 0.0 and not params.logit_bias
+            and not (params.repetition_penalty
+                     and params.repetition_penalty != 1.0))
+
+
+def penalty_window(params: SamplingParams) -> Optional[int]:
+    """Tokens of context the request's repetition penalty looks at: 0
+    without a penalty, None when the whole context counts."""
+    if not (params.repetition_penalty
+            and params.repetition_penalty != 1.0):
+        return 0
+    return params.repetition_context_size or None
+
+
+def device_sampled(params: SamplingParams, *, on_gpu: bool, native: bool,
+                   disabled: bool) -> bool:
+    """Whether a request's rows are sampled by the batched
+    ``ops.sample_rows`` kernel.  on_gpu: the pool is on a GPU; native: the
+    HIP extension is live (not MLXS_AMD_FORCE_TORCH); disabled:
+    MLXS_AMD_NO_FUSED_SAMPLE is set.  Seeded requests draw from their CPU
+    generator and plain-greedy ones from the batched argmax; a bias table
+    or penalty window beyond the kernel's limits keeps the per-row path."""
+    window = penalty_window(params)
+    return (on_gpu and native and not disabled
+            and params.seed is None
+            and not plain_greedy(params)
+            and len(params.logit_bias or ()) <= ops.SAMPLE_ROWS_MAX_BIAS
+            and window is not None
+            and window <= ops.SAMPLE_ROWS_MAX_WINDOW)
+
+
+def fused_sample_disabled() -> bool:
+    return bool(os.environ.get("MLXS_AMD_NO_FUSED_SAMPLE"))
+
+
 class _Request:
     def __init__(self, prompt_ids: List[int], params: SamplingParams):
         self.prompt = prompt_ids
@@ -67,10 +105,96 @@ class _Request:
         if params.seed is not None:
             self.gen = torch.Generator(device="cpu").manual_seed(params.seed)
         # plain greedy rows share one batched on-device argmax
-        self.plain_greedy = (
-            params.temperature <= 0.0 and not params.logit_bias
-            and not (params.repetition_penalty
-                     and params.repetition_penalty != 1.0))
+        self.plain_greedy = plain_greedy(params)
+        # sampled by ops.sample_rows; decided at admission
+        self.on_device = False
+
+
+class _RowSampler:
+    """Device state of the batched sampler: per-slot parameter vectors
+    (written at admission, cleared at release), the uniform draws and the
+    logsumexp the kernel leaves for the streams' logprobs."""
+
+    def __init__(self, B: int, dev):
+        NB, W = ops.SAMPLE_ROWS_MAX_BIAS, ops.SAMPLE_ROWS_MAX_WINDOW
+        f32, i32 = torch.float32, torch.int32
+        self.temperature = torch.zeros(B, dtype=f32, device=dev)
+        self.top_p = torch.ones(B, dtype=f32, device=dev)
+        self.penalty = torch.ones(B, dtype=f32, device=dev)
+        self.active = torch.zeros(B, dtype=i32, device=dev)
+        self.u = torch.zeros(B, dtype=f32, device=dev)
+        self.lse = torch.zeros(B, dtype=f32, device=dev)
+        self.bias_idx = torch.full((B, NB), -1, dtype=i32, device=dev)
+        self.bias_val = torch.zeros(B, NB, dtype=f32, device=dev)
+        self.pen_idx = torch.full((B, W), -1, dtype=i32, device=dev)
+        self.one = torch.ones(1, dtype=i32, device=dev)
+        self.rows: set = set()        # slots of device-sampled requests
+        self.bias_rows: set = set()   # ... with a logit_bias
+        self.pen_rows: set = set()    # ... with a repetition penalty
+
+    def admit(self, b: int, p: SamplingParams):
+        self.rows.add(b)
+        self.temperature[b].fill_(max(float(p.temperature), 0.0))
+        self.top_p[b].fill_(float(p.top_p))
+        self.active[b].fill_(1)
+        if p.logit_bias:
+            n = len(p.logit_bias)
+            self.bias_idx[b, :n].copy_(torch.tensor(
+                list(p.logit_bias.keys()), dtype=torch.int32), True)
+            self.bias_val[b, :n].copy_(torch.tensor(
+                list(p.logit_bias.values()), dtype=torch.float32), True)
+            self.bias_rows.add(b)
+        if penalty_window(p):
+            self.penalty[b].fill_(float(p.repetition_penalty))
+            self.pen_rows.add(b)
+
+    def release(self, b: int):
+        if b not in self.rows:
+            return
+        self.rows.discard(b)
+        self.temperature[b].zero_()
+        self.top_p[b].fill_(1.0)
+        self.active[b].zero_()
+        if b in self.bias_rows:
+            self.bias_rows.discard(b)
+            self.bias_idx[b].fill_(-1)
+            self.bias_val[b].zero_()
+        if b in self.pen_rows:
+            self.pen_rows.discard(b)
+            self.penalty[b].fill_(1.0)
+            self.pen_idx[b].fill_(-1)
+
+    @staticmethod
+    def _window(req: "_Request") -> List[int]:
+        W = ops.SAMPLE_ROWS_MAX_WINDOW
+        win = req.rep_context[-req.params.repetition_context_size:]
+        return win + [-1] * (W - len(win))
+
+    def sample(self, logits: torch.Tensor, tok: torch.Tensor, slots,
+               b: Optional[int] = None):
+        """One launch over the pool's logits [B, V] (b is None), or over
+        the [1, V] prefill logits of slot ``b``.  Leaves the ids in
+        ``tok`` and the logsumexp of the edited rows in ``self.lse``."""
+        W = ops.SAMPLE_ROWS_MAX_WINDOW
+        rows = slice(None) if b is None else slice(b, b + 1)
+        pen_rows = self.pen_rows if b is None else self.pen_rows & {b}
+        bias_rows = self.bias_rows if b is None else self.bias_rows & {b}
+        self.u[rows].uniform_()
+        if pen_rows:
+            # the windows move every step: one upload for the batch
+            pad = [-1] * W
+            host = [self._window(slots[i]) if i in pen_rows else pad
+                    for i in (range(len(slots)) if b is None else (b,))]
+            self.pen_idx[rows].copy_(
+                torch.tensor(host, dtype=torch.int32), non_blocking=True)
+        ops.sample_rows(
+            logits, self.temperature[rows], self.top_p[rows], self.u[rows],
+            self.active if b is None else self.one, tok[rows],
+            self.lse[rows],
+            self.bias_idx[rows] if bias_rows else None,
+            self.bias_val[rows] if bias_rows else None,
+            self.pen_idx[rows] if pen_rows else None,
+            self.penalty[rows] if pen_rows else None)
 
 
 class TokenStream:
@@ -156,6 +280,9 @@ class BatchScheduler:
         self._graph = None
         self._logits_out: Optional[torch.Tensor] = None
         self.graphed = False
+        # batched sampler state; only where ops.sample_rows has a kernel
+        self._sampler: Optional[_RowSampler] = (
+            _RowSampler(B, dev) if ops.use_native(self.tok) else None)
         self._m = metrics.batching_metrics()
         self._thread = threading.Thread(target=self._run, daemon=True,
                                         name="batch-scheduler")
@@ -262,6 +389,8 @@ class BatchScheduler:
     def _release(self, b: int):
         self._slots[b] = None
         self._pos_host[b] = 0
+        if self._sampler is not None:
+            self._sampler.release(b)
         self.tok[b].zero_()
         self.pos[b].zero_()
         self.inc[b].zero_()
@@ -282,10 +411,28 @@ class BatchScheduler:
         self.pos[b].fill_(T)
         self.inc[b].fill_(1)
         logits = h[:, -1, :].float()
+        req.on_device = self._on_device(req.params, logits.shape[-1])
+        if req.on_device:
+            # the first token through the batched sampler at B = 1
+            self._sampler.admit(b, req.params)
+            logits = logits.contiguous()
+            self._sampler.sample(logits, self.tok, self._slots, b)
+            self._emit(b, req, logits, None, int(self.tok[b].item()), row=0,
+                       fed=True)
+            return
         lse = torch.logsumexp(logits, dim=-1, keepdim=True)
         am = logits.argmax(-1).tolist() if req.plain_greedy else None
         self._emit(b, req, logits, lse, am[0] if am else None, row=0,
                    fed=False)
+
+    def _on_device(self, p: SamplingParams, vocab: int) -> bool:
+        return (self._sampler is not None
+                and device_sampled(p, on_gpu=True,
+                                   native=ops.use_native(self.tok),
+                                   disabled=fused_sample_disabled())
+                # the per-row path wraps negative keys and raises on
+                # keys past the vocabulary: leave both to it
+                and all(0 <= int(k) < vocab for k in (p.logit_bias or ())))
 
     def _step(self) -> torch.Tensor:
         h = self.model(self.tok, self.caches)
@@ -305,24 +452,37 @@ class BatchScheduler:
         # greedy feed for every running row in one device op (inc masks
         # idle rows back to token 0); other rows are overwritten below
         self.tok.copy_((am * self.inc).view(-1, 1))
-        am_host = am.tolist()
+        if self._sampler is not None and self._sampler.rows:
+            # one launch samples every device row into tok, over the
+            # greedy feed; greedy rows read their argmax back from tok too
+            # (inc is 1 on every running row), so the step still has one
+            # readback
+            self._sampler.sample(logits, self.tok, self._slots)
+            am_host = self.tok.view(-1).tolist()
+        else:
+            am_host = am.tolist()
         for b, req in enumerate(self._slots):
             if req is None:
                 continue
             self._pos_host[b] += 1
             self._emit(b, req, logits, lse, am_host[b], row=b,
-                       fed=req.plain_greedy)
+                       fed=req.plain_greedy or req.on_device)
 
     def _emit(self, b: int, req: _Request, logits: torch.Tensor,
               lse: torch.Tensor, greedy_tok: Optional[int], row: int,
               fed: bool):
         """Sample slot ``b``'s next token from ``logits[row]``, hand it to
         the request and make it the slot's next input (``fed``: the
-        batched argmax already wrote it)."""
+        batched argmax or the batched sampler already wrote it;
+        ``greedy_tok`` is that token)"""
         p = req.params
         if req.plain_greedy:
             tid = greedy_tok
             logprobs = logits[row] - lse[row]
+        elif req.on_device:
+            # sample_rows edited the row in place and left its logsumexp
+            tid = greedy_tok
+            logprobs = logits[row] - self._sampler.lse[b]
         else:
             # the per-request path of engine.generate_step
             lg = logits[row: row + 1].clone()

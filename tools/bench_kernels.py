@@ -280,9 +280,61 @@ def bench_fp8_prefill(ops, ext, dev="cuda", windows=3, iters=3):
         os.environ.pop(k, None)
 
 
+def bench_sample(ops, dev="cuda", windows=3, iters=20):
+    """Batched sampling at DeepSeek-V3's vocabulary (V = 129 280), B in
+    {1, 16, 64}, temperature 0.8, top_p in {1.0, 0.9}: one sample_rows
+    launch (with its uniform_ and the step's one readback of the ids)
+    against the per-row path of BatchScheduler._emit (row clone,
+    logsumexp, ops.sample, .item() per row).  Same process, alternating,
+    `windows` timed windows of `iters` steps after a warm-up; prints
+    median and min-max us per step."""
+    V, T = 129280, 0.8
+    g = torch.Generator(device=dev).manual_seed(5)
+    print(f"batched sampling, V={V}, temperature {T}: us per decode step")
+    for B in (1, 16, 64):
+        logits = torch.randn(B, V, device=dev, generator=g) * 3
+        temperature = torch.full((B,), T, device=dev)
+        u = torch.zeros(B, device=dev)
+        active = torch.ones(B, dtype=torch.int32, device=dev)
+        tok = torch.zeros(B, 1, dtype=torch.int64, device=dev)
+        lse = torch.zeros(B, device=dev)
+        for tp in (1.0, 0.9):
+            top_p = torch.full((B,), tp, device=dev)
+
+            def kernel():
+                u.uniform_()
+                ops.sample_rows(logits, temperature, top_p, u, active, tok,
+                                lse)
+                return tok.view(-1).tolist()
+
+            def per_row():
+                out = []
+                for b in range(B):
+                    lg = logits[b: b + 1].clone()
+                    lp = lg - torch.logsumexp(lg, dim=-1, keepdim=True)
+                    out.append(int(ops.sample(lg, T, tp).item()))
+                return out, lp
+
+            ts = {"kernel": [], "per-row": []}
+            fns = {"kernel": kernel, "per-row": per_row}
+            for fn in fns.values():
+                timeit(fn, 3, warmup=2)
+            for _ in range(windows):  # alternate the two paths
+                for name, fn in fns.items():
+                    ts[name].append(timeit(fn, iters, warmup=0))
+            for name, v in ts.items():
+                v.sort()
+                print(f"  B={B:2d} top_p={tp:.1f} {name:8s} median "
+                      f"{v[len(v) // 2]:9.1f} us  min {v[0]:9.1f}  "
+                      f"max {v[-1]:9.1f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--sample", action="store_true",
+                    help="only the batched sampling comparison: the "
+                         "sample_rows kernel vs the per-row torch path")
     ap.add_argument("--fp8-prefill", action="store_true",
                     help="only the FP8 MoE prefill comparison: packed "
                          "wide-tile route vs dequant per call")
@@ -301,6 +353,9 @@ def main():
     dev = "cuda"
     torch.manual_seed(0)
 
+    if args.sample:
+        bench_sample(ops, dev)
+        return
     if args.gate_only:
         bench_grouped_gate(ops, ref, args.iters, dev)
         return

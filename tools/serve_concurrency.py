@@ -3,9 +3,10 @@ request streams against one BatchScheduler (no HTTP), seeded prompt ids.
 
     python tools/serve_concurrency.py deepseek-v2-lite --streams 8
 
-``--max-batch`` defaults to the stream count.  Prints aggregate tok/s
-(all generated tokens over the wall time of the whole wave), per-stream
-decode tok/s and the p50 time to first token."""
+``--max-batch`` defaults to the stream count; ``--temperature`` and
+``--top-p`` make every stream a sampled (unseeded) request.  Prints
+aggregate tok/s (all generated tokens over the wall time of the whole
+wave), per-stream decode tok/s and the p50 time to first token."""
 import argparse
 import pathlib
 import statistics
@@ -28,6 +29,9 @@ ap.add_argument("--max-batch", type=int, default=0)
 ap.add_argument("--prompt-len", type=int, default=128)
 ap.add_argument("--tokens", type=int, default=200)
 ap.add_argument("--capacity", type=int, default=1024)
+ap.add_argument("--temperature", type=float, default=0.0,
+                help="sampling temperature of every stream (0: greedy)")
+ap.add_argument("--top-p", type=float, default=1.0)
 args = ap.parse_args()
 max_batch = args.max_batch or args.streams
 
@@ -48,7 +52,9 @@ def wave(n_tok):
     def run(i):
         t0 = time.perf_counter()
         t_first, n = t0, 0
-        for _ in sched.submit(prompts[i], SamplingParams(max_tokens=n_tok)):
+        for _ in sched.submit(prompts[i], SamplingParams(
+                max_tokens=n_tok, temperature=args.temperature,
+                top_p=args.top_p)):
             if n == 0:
                 t_first = time.perf_counter()
             n += 1
@@ -70,6 +76,7 @@ total = sum(n for n, _, _ in res)
 per = [(n - 1) / d for n, _, d in res if n > 1]
 ttft = statistics.median(t for _, t, _ in res)
 print(f"{args.preset}: streams={args.streams} max_batch={max_batch} "
+      f"temperature={args.temperature} top_p={args.top_p} "
       f"aggregate {total / wall:.1f} tok/s, per-stream decode "
       f"{statistics.mean(per):.1f} tok/s (min {min(per):.1f}), "
       f"p50 TTFT {ttft * 1000:.1f} ms, {total} tokens in {wall:.2f} s "
