@@ -214,6 +214,13 @@ class MLAAttention(nn.Module):
                 and dk % 8 == 0 and self.kv_lora_rank % 8 == 0
                 and ext.attn_decode_shape_ok(self.n_heads, self.kv_lora_rank))
 
+    def _mla_mfma(self, x) -> bool:
+        """T == 1 absorbed attention goes to the MFMA kernel: native
+        path, a shape it serves (32 / 64 / 128 heads), not switched off."""
+        return (ops.use_native(x) and ops.mla_decode_enabled()
+                and ops.mla_decode_shape_ok(self.n_heads, self.kv_lora_rank,
+                                            self.qk_rope))
+
     def _ensure_absorb(self, device, dtype):
         if self._w_uk is not None:
             return
@@ -291,13 +298,19 @@ class MLAAttention(nn.Module):
             # q absorb: [nh, B, nope] @ [nh, nope, rank] -> [nh, B, rank]
             qn = q_nope.permute(2, 0, 1, 3).reshape(nh, B * T, self.qk_nope)
             q_abs = torch.bmm(qn, self._w_uk)           # [nh, B, rank]
-            qf = torch.cat([q_abs.view(nh, B, T, rank).permute(1, 0, 2, 3),
-                            q_pe.transpose(1, 2)], dim=-1)  # [B,nh,1,rank+rope]
-            o = ops.attention(qf, k_all, k_all[..., :rank], self.scale,
-                              causal_offset=offset, pos_dev=gp)  # [B,nh,1,rank]
+            if self._mla_mfma(x):
+                o = ops.mla_decode(q_abs.transpose(0, 1), q_pe[:, 0], k_all,
+                                   rank, self.scale, gp)    # [nh, B, rank]
+            else:
+                qf = torch.cat(
+                    [q_abs.view(nh, B, T, rank).permute(1, 0, 2, 3),
+                     q_pe.transpose(1, 2)], dim=-1)  # [B,nh,1,rank+rope]
+                o = ops.attention(qf, k_all, k_all[..., :rank], self.scale,
+                                  causal_offset=offset,
+                                  pos_dev=gp)        # [B,nh,1,rank]
+                o = o.permute(1, 0, 2, 3).reshape(nh, B * T, rank)
             # out absorb: [nh, B, rank] @ [nh, rank, vd] -> [nh, B, vd]
-            ov = torch.bmm(o.permute(1, 0, 2, 3).reshape(nh, B * T, rank),
-                           self._w_uv)
+            ov = torch.bmm(o, self._w_uv)
             out = ov.view(nh, B, T, self.v_head_dim).permute(1, 2, 0, 3)
             return self.o_proj(out.reshape(B, T, -1))
 
@@ -341,9 +354,13 @@ class MLAAttention(nn.Module):
             self.qk_rope)
         self._ensure_absorb(qh.device, qh.dtype)
         q_abs = torch.bmm(qn, self._w_uk)               # [nh, B, rank]
-        o = ops.hip_ext().attn_decode_split(
-            q_abs.transpose(0, 1), q_pe, k_all, k_all[..., :rank],
-            self.scale, 0.0, 0, gp)                     # [nh, B, rank]
+        if self._mla_mfma(qh):
+            o = ops.mla_decode(q_abs.transpose(0, 1), q_pe, k_all, rank,
+                               self.scale, gp)          # [nh, B, rank]
+        else:
+            o = ops.hip_ext().attn_decode_split(
+                q_abs.transpose(0, 1), q_pe, k_all, k_all[..., :rank],
+                self.scale, 0.0, 0, gp)                 # [nh, B, rank]
         ov = torch.bmm(o, self._w_uv)                   # [nh, B, vd]
         out = ov.view(nh, B, 1, self.v_head_dim).permute(1, 2, 0, 3)
         return self.o_proj(out.reshape(B, 1, -1))

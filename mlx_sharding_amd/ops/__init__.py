@@ -159,6 +159,40 @@ def attention(q, k, v, scale: float, causal_offset: int = 0,
     return ref.attention(q, k, v, scale, causal_offset, softcap, sliding_window)
 
 
+def mla_decode_enabled() -> bool:
+    """The MFMA absorbed-MLA decode kernel (mla_decode.hip) serves the
+    shapes it supports.  MLXS_AMD_NO_MLA_MFMA=1 keeps them on the
+    head-group attn_decode kernel for A/B in one build."""
+    return not os.environ.get("MLXS_AMD_NO_MLA_MFMA")
+
+
+def mla_decode_shape_ok(n_heads: int, rank: int, rope: int) -> bool:
+    """True when the MFMA kernel has an instantiation for this absorbed
+    shape (Hq heads over rows of rank + rope, V = the first rank
+    columns)."""
+    ext = _load_ext()
+    return ext is not None and ext.mla_decode_shape_ok(n_heads, rank + rope,
+                                                       rank)
+
+
+def mla_decode(q_nope, q_rope, kv, rank: int, scale: float, pos_dev=None):
+    """Absorbed-MLA decode attention (T == 1, one KV head) over the
+    compressed cache.
+
+    q_nope [B, Hq, rank] and q_rope [B, Hq, rope] are views with any
+    batch/head strides; kv is the cache view [B, 1, S, rank+rope] whose
+    first ``rank`` columns are V.  ``pos_dev`` (int32 [1] or [B] on
+    device) makes kv the full capacity buffer with row b attending over
+    its first pos[b]+1 keys.  Returns head-major [Hq, B, rank]."""
+    if _use_hip(q_nope):
+        return _require_ext("mla_decode").mla_decode(q_nope, q_rope, kv, rank,
+                                                     scale, pos_dev)
+    q = torch.cat([q_nope, q_rope], dim=-1).unsqueeze(2)
+    o = attention(q, kv, kv[..., :rank], scale,
+                  causal_offset=kv.shape[2] - 1, pos_dev=pos_dev)
+    return o[:, :, 0].transpose(0, 1).contiguous()
+
+
 def _prefill_attention_gpu(q, k, v, scale, causal_offset, softcap, sliding_window):
     """Prefill path: QK^T and PV on hipBLASLt (library GEMMs), mask +
     softmax in fp32.  (Flash-prefill HIP kernel is the planned upgrade.)"""

@@ -363,6 +363,18 @@ extern "C" void launch_attn_decode(const void* q, const void* q_rope,
   }
 }
 
+// The split-S combiner for other decode kernels that write the same
+// partial layout (mla_decode.hip).
+extern "C" void launch_attn_decode_combine(const float* part_o,
+                                           const float* part_ml, void* out,
+                                           int nsplit, int B, int Hq, int Dv,
+                                           long o_bs, long o_hs,
+                                           hipStream_t stream) {
+  attn_decode_combine_kernel<<<dim3((unsigned)(B * Hq)), dim3(128), 0,
+                               stream>>>(part_o, part_ml, (short*)out, nsplit,
+                                         Dv, Hq, o_bs, o_hs);
+}
+
 extern "C" bool attn_decode_supported_shape(int G, int Dv) {
   if (Dv > 512) return false;
   const int dvt = (Dv + AD_BLOCK - 1) / AD_BLOCK;

@@ -38,6 +38,11 @@ void launch_attn_decode(const void*, const void*, const void*, const void*,
                         int, int, long, int, int, long, float, float, int,
                         int, long, long, long, long, long, long, hipStream_t);
 bool attn_decode_supported_shape(int, int);
+void launch_mla_decode(const void*, const void*, const void*, void*, float*,
+                       float*, int, const int*, int, int, int, int, long, int,
+                       int, float, long, long, long, long, hipStream_t);
+bool mla_decode_supported_shape(int, int, int);
+int mla_decode_nsplit(int, int, long);
 void launch_attn_prefill(const void*, const void*, const void*, void*, int,
                          int, int, int, int, long, long, int, int, float,
                          float, int, int, hipStream_t);
@@ -542,6 +547,68 @@ torch::Tensor attn_decode_split(torch::Tensor q_nope, torch::Tensor q_rope,
               "q rows must be contiguous");
   return attn_decode_impl(q_nope, q_rope, k, v, scale, softcap, window, pos,
                           true);
+}
+
+// MFMA flash-decode for absorbed MLA (mla_decode.hip).  q_nope
+// [B, Hq, rank] and q_rope [B, Hq, rope] are read in place through their
+// (batch, head) strides; kv is the compressed cache view [B, 1, S, Dk]
+// over a [B, 1, Scap, Dk] buffer with V = kv[..., :rank].  Returns
+// head-major [Hq, B, rank].
+torch::Tensor mla_decode(torch::Tensor q_nope, torch::Tensor q_rope,
+                         torch::Tensor kv, int64_t rank, double scale,
+                         c10::optional<torch::Tensor> pos) {
+  check_bf16(q_nope, "q_nope");
+  check_bf16(q_rope, "q_rope");
+  check_bf16(kv, "kv");
+  TORCH_CHECK(q_nope.dim() == 3 && q_rope.dim() == 3 &&
+                  q_nope.size(0) == q_rope.size(0) &&
+                  q_nope.size(1) == q_rope.size(1),
+              "q_nope/q_rope must be [B, Hq, *] with matching B, Hq");
+  TORCH_CHECK(kv.dim() == 4 && kv.size(1) == 1,
+              "mla_decode needs one KV head (Hkv == 1)");
+  const int B = q_nope.size(0), Hq = q_nope.size(1);
+  const int Dv = q_nope.size(2), Dk = Dv + (int)q_rope.size(2);
+  TORCH_CHECK(kv.size(0) >= B, "kv batch smaller than q batch");
+  TORCH_CHECK(rank == Dv && kv.size(3) == Dk,
+              "row geometry mismatch: rank ", rank, ", q ", Dv, "+",
+              q_rope.size(2), ", kv row ", kv.size(3));
+  TORCH_CHECK(mla_decode_supported_shape(Hq, Dk, Dv),
+              "mla_decode: unsupported shape Hq=", Hq, " Dk=", Dk, " Dv=", Dv);
+  TORCH_CHECK(q_nope.stride(2) == 1 && q_rope.stride(2) == 1,
+              "q rows must be contiguous");
+  TORCH_CHECK(kv.stride(3) == 1 && kv.stride(2) == Dk,
+              "kv rows must be contiguous with row stride Dk");
+  // the kernel reads q and kv with 16-byte loads
+  auto al16 = [](const torch::Tensor& t) {
+    return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0 &&
+           t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0;
+  };
+  TORCH_CHECK(al16(q_nope) && al16(q_rope) && al16(kv),
+              "q/kv rows must be 16-byte aligned");
+  const int S = kv.size(2);
+  const long Scap = B > 1 ? kv.stride(0) / Dk : kv.stride(1) / Dk;
+  TORCH_CHECK(Scap >= S && Scap * Dk == (B > 1 ? kv.stride(0) : kv.stride(1)),
+              "kv batch stride must be a whole number of rows");
+  int sbs;
+  const int* s_ptr = pos_arg(pos, B, sbs);
+  const int nsplit = mla_decode_nsplit(B, Hq, s_ptr ? Scap : (long)S);
+  auto out = torch::empty({Hq, B, Dv}, q_nope.options());
+  float* part_o = nullptr;
+  float* part_ml = nullptr;
+  torch::Tensor po, pml;
+  if (nsplit > 1) {
+    auto fopts = q_nope.options().dtype(torch::kFloat32);
+    po = torch::empty({(long)B * Hq * nsplit * Dv}, fopts);
+    pml = torch::empty({(long)B * Hq * nsplit * 2}, fopts);
+    part_o = po.data_ptr<float>();
+    part_ml = pml.data_ptr<float>();
+  }
+  launch_mla_decode(q_nope.data_ptr(), q_rope.data_ptr(), kv.data_ptr(),
+                    out.data_ptr(), part_o, part_ml, nsplit, s_ptr, sbs, B,
+                    Hq, S, Scap, Dk, Dv, (float)scale, q_nope.stride(0),
+                    q_nope.stride(1), q_rope.stride(0), q_rope.stride(1),
+                    cur_stream());
+  return out;
 }
 
 // q [B, Hq, T, Dk]; k/v cache views [B, Hkv, S, D] (row-contiguous)
@@ -1328,6 +1395,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("window"), pybind11::arg("pos") = pybind11::none());
   m.def("attn_decode_shape_ok", [](int64_t g, int64_t dv) {
     return attn_decode_supported_shape((int)g, (int)dv);
+  });
+  m.def("mla_decode", &mla_decode, pybind11::arg("q_nope"),
+        pybind11::arg("q_rope"), pybind11::arg("kv"), pybind11::arg("rank"),
+        pybind11::arg("scale"), pybind11::arg("pos") = pybind11::none());
+  m.def("mla_decode_shape_ok", [](int64_t hq, int64_t dk, int64_t dv) {
+    return mla_decode_supported_shape((int)hq, (int)dk, (int)dv);
+  });
+  m.def("mla_decode_nsplit", [](int64_t B, int64_t hq, int64_t span) {
+    return mla_decode_nsplit((int)B, (int)hq, (long)span);
   });
   m.def("attn_prefill", &attn_prefill);
   m.def("attn_prefill_shape_ok", [](int64_t dk, int64_t dv) {

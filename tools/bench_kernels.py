@@ -96,6 +96,50 @@ def bench_v3(ops, ext, dev="cuda"):
               f"~{kv_bytes / (med / 1e6) / 1e12:.2f} TB/s of one K pass")
 
 
+# vendor-published MI355X peaks, for the share-of-bound column
+_PEAK_HBM = 8.0e12        # B/s
+_PEAK_BF16 = 2.5e15       # dense bf16 matrix FLOP/s
+
+
+def bench_mla(ops, ext, dev="cuda", iters=200):
+    """Absorbed MLA decode at B=64, Hq=128, Dk=576, Dv=512: the head-group
+    attn_decode_split kernel and the MFMA mla_decode kernel, alternated in
+    one process after warm-up, with a host-side S and with a device [B]
+    position over a capacity-S buffer.  Median of five windows between
+    device events (min-max).  The bound is the larger of the one-pass KV
+    bytes over peak HBM bandwidth and the QK+PV FLOPs over peak bf16."""
+    B, Hq, Dk, Dv = 64, 128, 576, 512
+    scale = Dk ** -0.5
+    q_abs = torch.randn(Hq, B, Dv, dtype=torch.bfloat16, device=dev)
+    q_pe = torch.randn(B, Hq, Dk - Dv, dtype=torch.bfloat16, device=dev)
+    qn = q_abs.transpose(0, 1)
+    for S in (512, 4096):
+        kv = torch.randn(B, 1, S, Dk, dtype=torch.bfloat16, device=dev) * 0.5
+        v = kv[..., :Dv]
+        nbytes = B * S * Dk * 2
+        flops = 2 * B * Hq * S * (Dk + Dv)
+        t_mem, t_mma = nbytes / _PEAK_HBM * 1e6, flops / _PEAK_BF16 * 1e6
+        bound, which = max((t_mem, "HBM"), (t_mma, "MFMA"))
+        for mode in ("host", "device"):
+            pos = None if mode == "host" else torch.full(
+                (B,), S - 1, dtype=torch.int32, device=dev)
+            fns = (("attn_decode_split", lambda: ext.attn_decode_split(
+                        qn, q_pe, kv, v, scale, 0.0, 0, pos)),
+                   ("mla_decode", lambda: ext.mla_decode(
+                        qn, q_pe, kv, Dv, scale, pos)))
+            diff = (fns[0][1]().float() - fns[1][1]().float()).abs().max()
+            print(f"S={S} {mode}: max |old - new| = {diff.item():.3e}, "
+                  f"mla_decode_nsplit = "
+                  f"{ext.mla_decode_nsplit(B, Hq, S)}")
+            for rnd in range(2):  # alternate the two kernels
+                for name, fn in fns:
+                    med, lo, hi = _repeat(fn, iters)
+                    print(f"{name:18s} S={S:5d} {mode:6s} round {rnd}: "
+                          f"median {med:8.1f} us  min {lo:8.1f}  "
+                          f"max {hi:8.1f}  bound {bound:5.1f} us ({which}) "
+                          f"-> {100 * bound / med:5.1f}%")
+
+
 def bench_fp8(ops, ext, dev="cuda", E=64, windows=3):
     """FP8 block-quantized kernels against the 8-bit affine (gs 128)
     fp16-dequant kernels, which stream the same weight bytes: DeepSeek-V3
@@ -345,6 +389,9 @@ def main():
     ap.add_argument("--v3-only", action="store_true",
                     help="only the DeepSeek-V3 gate and 128-head attention "
                          "lines")
+    ap.add_argument("--mla-only", action="store_true",
+                    help="only the 128-head absorbed-MLA decode comparison: "
+                         "attn_decode_split vs the MFMA mla_decode kernel")
     args = ap.parse_args()
     from mlx_sharding_amd import ops
     from mlx_sharding_amd.ops import reference as ref
@@ -353,6 +400,9 @@ def main():
     dev = "cuda"
     torch.manual_seed(0)
 
+    if args.mla_only:
+        bench_mla(ops, ext, dev)
+        return
     if args.sample:
         bench_sample(ops, dev)
         return
