@@ -149,6 +149,23 @@ class _StackedLinear(nn.Module):
         return torch.stack(outs)
 
 
+# Most new tokens a forward over a cached prefix attends in absorbed form
+# (ops.mla_chunk over the compressed cache) instead of re-expanding the
+# whole prefix.  The arithmetic break-even is 170 tokens for the shipped
+# geometries; 64 is the largest T measured (docs/PERFORMANCE.md).
+MLA_CHUNK_MAX_T = 64
+
+
+def mla_chunk_route(native: bool, graph_pos, offset: int, T: int,
+                    served: bool, enabled: bool,
+                    max_t: int = MLA_CHUNK_MAX_T) -> bool:
+    """A T-token forward takes the absorbed chunk route: native path, a
+    host-side position, a cached prefix to attend, a short chunk, a shape
+    the kernel serves, not switched off."""
+    return bool(native and graph_pos is None and offset > 0
+                and 2 <= T <= max_t and served and enabled)
+
+
 class MLAAttention(nn.Module):
     # Most heads the compressed-cache (absorbed) decode is taken for.  The
     # kernel also runs 32/64/128 heads as 8-head groups; only model
@@ -261,7 +278,9 @@ class MLAAttention(nn.Module):
         absorbed through W_UK/W_UV; prefill expands K/V from the
         compressed prefix with kv_b_proj and runs the MFMA prefill
         kernel (the standard MLA split: expanded MHA at prefill,
-        absorbed MQA at decode)."""
+        absorbed MQA at decode).  A short chunk over a cached prefix
+        (mla_chunk_route) is absorbed too and attends the compressed
+        rows through ops.mla_chunk."""
         B, T, _ = x.shape
         nh, rank, rope = self.n_heads, self.kv_lora_rank, self.qk_rope
         qh, ckv = self._project_q(x)
@@ -311,6 +330,21 @@ class MLAAttention(nn.Module):
                 o = o.permute(1, 0, 2, 3).reshape(nh, B * T, rank)
             # out absorb: [nh, B, rank] @ [nh, rank, vd] -> [nh, B, vd]
             ov = torch.bmm(o, self._w_uv)
+            out = ov.view(nh, B, T, self.v_head_dim).permute(1, 2, 0, 3)
+            return self.o_proj(out.reshape(B, T, -1))
+
+        if mla_chunk_route(ops.use_native(x), gp, offset, T,
+                           ops.mla_chunk_shape_ok(nh, rank, rope),
+                           ops.mla_chunk_enabled()):
+            # a short tail over a cached prefix: attend the compressed
+            # rows directly instead of re-expanding the whole prefix
+            self._ensure_absorb(x.device, x.dtype)
+            qn = q_nope.permute(2, 0, 1, 3).reshape(nh, B * T, self.qk_nope)
+            q_abs = torch.bmm(qn, self._w_uk)           # [nh, B*T, rank]
+            o = ops.mla_chunk(q_abs.view(nh, B, T, rank).permute(1, 2, 0, 3),
+                              q_pe, k_all, rank, self.scale)  # [B,T,nh,rank]
+            ov = torch.bmm(o.view(B * T, nh, rank).transpose(0, 1),
+                           self._w_uv)                  # [nh, B*T, vd]
             out = ov.view(nh, B, T, self.v_head_dim).permute(1, 2, 0, 3)
             return self.o_proj(out.reshape(B, T, -1))
 

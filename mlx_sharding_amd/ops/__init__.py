@@ -193,6 +193,40 @@ def mla_decode(q_nope, q_rope, kv, rank: int, scale: float, pos_dev=None):
     return o[:, :, 0].transpose(0, 1).contiguous()
 
 
+def mla_chunk_enabled() -> bool:
+    """Short prefills over a cached prefix attend the compressed cache
+    directly through the MFMA chunk kernel (mla_chunk.hip).
+    MLXS_AMD_NO_MLA_CHUNK=1 keeps them on the expand-the-prefix prefill
+    for A/B in one build."""
+    return not os.environ.get("MLXS_AMD_NO_MLA_CHUNK")
+
+
+def mla_chunk_shape_ok(n_heads: int, rank: int, rope: int) -> bool:
+    """True when the chunk kernel has an instantiation for this absorbed
+    shape (16 / 32 / 64 / 128 heads over rows of rank + rope)."""
+    ext = _load_ext()
+    return ext is not None and ext.mla_chunk_shape_ok(n_heads, rank + rope,
+                                                      rank)
+
+
+def mla_chunk(q_nope, q_rope, kv, rank: int, scale: float):
+    """Causal absorbed-MLA attention of T new tokens (one KV head) over the
+    compressed cache.
+
+    q_nope [B, T, Hq, rank] and q_rope [B, T, Hq, rope] are views with any
+    batch/token/head strides; kv is the cache view [B, 1, S, rank+rope]
+    whose last T rows are the new tokens and whose first ``rank`` columns
+    are V.  Token t attends keys [0, S - T + t].  Returns
+    [B, T, Hq, rank]."""
+    if _use_hip(q_nope):
+        return _require_ext("mla_chunk").mla_chunk(q_nope, q_rope, kv, rank,
+                                                   scale)
+    q = torch.cat([q_nope, q_rope], dim=-1).transpose(1, 2)
+    o = ref.attention(q, kv, kv[..., :rank], scale,
+                      causal_offset=kv.shape[2] - q.shape[2])
+    return o.transpose(1, 2).contiguous()
+
+
 def _prefill_attention_gpu(q, k, v, scale, causal_offset, softcap, sliding_window):
     """Prefill path: QK^T and PV on hipBLASLt (library GEMMs), mask +
     softmax in fp32.  (Flash-prefill HIP kernel is the planned upgrade.)"""

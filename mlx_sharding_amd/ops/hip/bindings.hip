@@ -43,6 +43,11 @@ void launch_mla_decode(const void*, const void*, const void*, void*, float*,
                        int, float, long, long, long, long, hipStream_t);
 bool mla_decode_supported_shape(int, int, int);
 int mla_decode_nsplit(int, int, long);
+void launch_mla_chunk(const void*, const void*, const void*, void*, float*,
+                      float*, int, int, int, int, int, long, int, int, float,
+                      long, long, long, long, long, long, hipStream_t);
+bool mla_chunk_supported_shape(int, int, int);
+int mla_chunk_nsplit(int, long, long);
 void launch_attn_prefill(const void*, const void*, const void*, void*, int,
                          int, int, int, int, long, long, int, int, float,
                          float, int, int, hipStream_t);
@@ -608,6 +613,71 @@ torch::Tensor mla_decode(torch::Tensor q_nope, torch::Tensor q_rope,
                     Hq, S, Scap, Dk, Dv, (float)scale, q_nope.stride(0),
                     q_nope.stride(1), q_rope.stride(0), q_rope.stride(1),
                     cur_stream());
+  return out;
+}
+
+// MFMA absorbed-MLA attention of T new tokens over the compressed cache
+// (mla_chunk.hip).  q_nope [B, T, Hq, rank] and q_rope [B, T, Hq, rope]
+// are read in place through their (batch, token, head) strides; kv is the
+// cache view [B, 1, S, Dk] over a [B, 1, Scap, Dk] buffer whose last T
+// rows are the new tokens, V = kv[..., :rank].  Token t attends keys
+// [0, S - T + t].  Returns [B, T, Hq, rank], contiguous.
+torch::Tensor mla_chunk(torch::Tensor q_nope, torch::Tensor q_rope,
+                        torch::Tensor kv, int64_t rank, double scale) {
+  check_bf16(q_nope, "q_nope");
+  check_bf16(q_rope, "q_rope");
+  check_bf16(kv, "kv");
+  TORCH_CHECK(q_nope.dim() == 4 && q_rope.dim() == 4 &&
+                  q_nope.size(0) == q_rope.size(0) &&
+                  q_nope.size(1) == q_rope.size(1) &&
+                  q_nope.size(2) == q_rope.size(2),
+              "q_nope/q_rope must be [B, T, Hq, *] with matching B, T, Hq");
+  TORCH_CHECK(kv.dim() == 4 && kv.size(1) == 1,
+              "mla_chunk needs one KV head (Hkv == 1)");
+  const int B = q_nope.size(0), T = q_nope.size(1), Hq = q_nope.size(2);
+  const int Dv = q_nope.size(3), Dk = Dv + (int)q_rope.size(3);
+  TORCH_CHECK(kv.size(0) >= B, "kv batch smaller than q batch");
+  TORCH_CHECK(rank == Dv && kv.size(3) == Dk,
+              "row geometry mismatch: rank ", rank, ", q ", Dv, "+",
+              q_rope.size(3), ", kv row ", kv.size(3));
+  TORCH_CHECK(mla_chunk_supported_shape(Hq, Dk, Dv),
+              "mla_chunk: unsupported shape Hq=", Hq, " Dk=", Dk, " Dv=", Dv);
+  const int S = kv.size(2);
+  TORCH_CHECK(T >= 1 && T <= S, "mla_chunk: T=", T,
+              " new tokens must be among the S=", S, " cached rows");
+  TORCH_CHECK(q_nope.stride(3) == 1 && q_rope.stride(3) == 1,
+              "q rows must be contiguous");
+  TORCH_CHECK(kv.stride(3) == 1 && kv.stride(2) == Dk,
+              "kv rows must be contiguous with row stride Dk");
+  // the kernel reads q and kv with 16-byte loads
+  auto al16 = [](const torch::Tensor& t) {
+    return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0 &&
+           t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+           t.stride(2) % 8 == 0;
+  };
+  TORCH_CHECK(al16(q_nope) && al16(q_rope) && al16(kv),
+              "q/kv rows must be 16-byte aligned");
+  const long Scap = B > 1 ? kv.stride(0) / Dk : kv.stride(1) / Dk;
+  TORCH_CHECK(Scap >= S && Scap * Dk == (B > 1 ? kv.stride(0) : kv.stride(1)),
+              "kv batch stride must be a whole number of rows");
+  const long rows = (long)T * Hq;
+  const int nsplit = mla_chunk_nsplit(B, rows, (long)S);
+  auto out = torch::empty({B, T, Hq, Dv}, q_nope.options());
+  float* part_o = nullptr;
+  float* part_ml = nullptr;
+  torch::Tensor po, pml;
+  if (nsplit > 1) {
+    auto fopts = q_nope.options().dtype(torch::kFloat32);
+    po = torch::empty({B * rows * nsplit * Dv}, fopts);
+    pml = torch::empty({B * rows * nsplit * 2}, fopts);
+    part_o = po.data_ptr<float>();
+    part_ml = pml.data_ptr<float>();
+  }
+  launch_mla_chunk(q_nope.data_ptr(), q_rope.data_ptr(), kv.data_ptr(),
+                   out.data_ptr(), part_o, part_ml, nsplit, B, T, Hq, S, Scap,
+                   Dk, Dv, (float)scale, q_nope.stride(0), q_nope.stride(1),
+                   q_nope.stride(2), q_rope.stride(0), q_rope.stride(1),
+                   q_rope.stride(2), cur_stream());
   return out;
 }
 
@@ -1404,6 +1474,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("mla_decode_nsplit", [](int64_t B, int64_t hq, int64_t span) {
     return mla_decode_nsplit((int)B, (int)hq, (long)span);
+  });
+  m.def("mla_chunk", &mla_chunk, pybind11::arg("q_nope"),
+        pybind11::arg("q_rope"), pybind11::arg("kv"), pybind11::arg("rank"),
+        pybind11::arg("scale"));
+  m.def("mla_chunk_shape_ok", [](int64_t hq, int64_t dk, int64_t dv) {
+    return mla_chunk_supported_shape((int)hq, (int)dk, (int)dv);
+  });
+  m.def("mla_chunk_nsplit", [](int64_t B, int64_t rows, int64_t span) {
+    return mla_chunk_nsplit((int)B, (long)rows, (long)span);
   });
   m.def("attn_prefill", &attn_prefill);
   m.def("attn_prefill_shape_ok", [](int64_t dk, int64_t dv) {

@@ -140,6 +140,74 @@ def bench_mla(ops, ext, dev="cuda", iters=200):
                           f"-> {100 * bound / med:5.1f}%")
 
 
+def bench_mla_chunk(ops, ext, dev="cuda", iters=200):
+    """One layer's attention section for T new tokens over a cached prefix
+    of a V2-Lite / V3 geometry (rows 576 / 512, nope 128, vd 128), B=1, two
+    ways alternated in one process after warm-up: the expanded path
+    (kv_b_proj over all S rows, mla_append_kv into per-head K/V temporaries,
+    attn_prefill) and the absorbed path (W_UK bmm, mla_chunk, W_UV bmm).
+    Median of five windows between device events (min-max).  The bound of
+    the absorbed path is the larger of one pass over the KV rows plus the
+    two absorb weights over peak HBM bandwidth and its FLOPs over peak
+    bf16."""
+    B, rank, rope, nope, vd = 1, 512, 64, 128, 128
+    scale = (nope + rope) ** -0.5
+    for nh in (16, 128):
+        w = (torch.randn(nh * (nope + vd), rank, device=dev) * rank ** -0.5
+             ).to(torch.bfloat16)
+        w3 = w.view(nh, nope + vd, rank)
+        w_uk = w3[:, :nope].contiguous()
+        w_uv = w3[:, nope:].transpose(1, 2).contiguous()
+        for S in (1024, 4096):
+            kv = (torch.randn(B, 1, S, rank + rope, device=dev) * 0.5
+                  ).to(torch.bfloat16)
+            for T in (8, 32, 64):
+                q_nope = torch.randn(B, T, nh, nope, dtype=torch.bfloat16,
+                                     device=dev)
+                q_pe = torch.randn(B, T, nh, rope, dtype=torch.bfloat16,
+                                   device=dev)
+
+                def expanded():
+                    kvh = torch.nn.functional.linear(
+                        kv[:, 0, :, :rank], w).view(B, S, nh, nope + vd)
+                    k = kvh.new_empty(B, nh, S, nope + rope)
+                    v = kvh.new_empty(B, nh, S, vd)
+                    ext.mla_append_kv(kvh, kv[:, 0, :, rank:], k, v, pos0=0)
+                    qf = torch.cat([q_nope, q_pe], dim=-1).transpose(1, 2)
+                    o = ops.attention(qf, k, v, scale, causal_offset=S - T)
+                    return o.transpose(1, 2).reshape(B, T, -1)
+
+                def absorbed():
+                    qn = q_nope.permute(2, 0, 1, 3).reshape(nh, B * T, nope)
+                    q_abs = torch.bmm(qn, w_uk)
+                    o = ext.mla_chunk(
+                        q_abs.view(nh, B, T, rank).permute(1, 2, 0, 3), q_pe,
+                        kv, rank, scale)
+                    ov = torch.bmm(o.view(B * T, nh, rank).transpose(0, 1),
+                                   w_uv)
+                    return ov.view(nh, B, T, vd).permute(1, 2, 0, 3).reshape(
+                        B, T, -1)
+
+                diff = (expanded().float() - absorbed().float()).abs().max()
+                nbytes = B * S * (rank + rope) * 2 + 2 * w_uk.numel() * 2
+                flops = (2 * B * T * nh * S * (2 * rank + rope)
+                         + 2 * B * T * nh * rank * (nope + vd))
+                t_mem = nbytes / _PEAK_HBM * 1e6
+                t_mma = flops / _PEAK_BF16 * 1e6
+                bound, which = max((t_mem, "HBM"), (t_mma, "MFMA"))
+                print(f"Hq={nh} S={S} T={T}: max |expanded - absorbed| = "
+                      f"{diff.item():.3e}, mla_chunk_nsplit = "
+                      f"{ext.mla_chunk_nsplit(B, T * nh, S)}, absorbed bound "
+                      f"{bound:.2f} us ({which})")
+                for rnd in range(2):  # alternate the two paths
+                    for name, fn in (("expanded", expanded),
+                                     ("absorbed", absorbed)):
+                        med, lo, hi = _repeat(fn, iters)
+                        print(f"{name:9s} Hq={nh:3d} S={S:5d} T={T:2d} round "
+                              f"{rnd}: median {med:8.1f} us  min {lo:8.1f}  "
+                              f"max {hi:8.1f}")
+
+
 def bench_fp8(ops, ext, dev="cuda", E=64, windows=3):
     """FP8 block-quantized kernels against the 8-bit affine (gs 128)
     fp16-dequant kernels, which stream the same weight bytes: DeepSeek-V3
@@ -392,6 +460,9 @@ def main():
     ap.add_argument("--mla-only", action="store_true",
                     help="only the 128-head absorbed-MLA decode comparison: "
                          "attn_decode_split vs the MFMA mla_decode kernel")
+    ap.add_argument("--mla-chunk", action="store_true",
+                    help="only the short-chunk-over-a-prefix comparison: "
+                         "expanded prefill vs the absorbed mla_chunk path")
     args = ap.parse_args()
     from mlx_sharding_amd import ops
     from mlx_sharding_amd.ops import reference as ref
@@ -402,6 +473,9 @@ def main():
 
     if args.mla_only:
         bench_mla(ops, ext, dev)
+        return
+    if args.mla_chunk:
+        bench_mla_chunk(ops, ext, dev)
         return
     if args.sample:
         bench_sample(ops, dev)
