@@ -94,10 +94,12 @@ class SwitchMLP(nn.Module):
             self.down_proj.weight, subs, max_tok, raw=raw)
 
     def forward(self, x_flat: torch.Tensor, weights: torch.Tensor,
-                indices: torch.Tensor) -> torch.Tensor:
+                indices: torch.Tensor, route=None) -> torch.Tensor:
+        """route: the ops.moe_route result that weights and indices come
+        from, when the fused prefill route built them."""
         if self._fp8:
             return ops.grouped_expert_mlp_fp8(x_flat, *self._fp8_pairs(),
-                                              weights, indices)
+                                              weights, indices, route=route)
         if self.quant is not None:
             g, u, d = self.gate_proj, self.up_proj, self.down_proj
             return ops.grouped_expert_mlp_quant(
@@ -105,10 +107,11 @@ class SwitchMLP(nn.Module):
                 (g.weight, g.scales, g.biases),
                 (u.weight, u.scales, u.biases),
                 (d.weight, d.scales, d.biases),
-                weights, indices, self.quant.group_size, self.quant.bits)
+                weights, indices, self.quant.group_size, self.quant.bits,
+                route=route)
         return ops.grouped_expert_mlp(
             x_flat, self.gate_proj.weight, self.up_proj.weight,
-            self.down_proj.weight, weights, indices)
+            self.down_proj.weight, weights, indices, route=route)
 
 
 class _StackedLinear(nn.Module):
@@ -491,6 +494,14 @@ class DeepseekV2MoE(nn.Module):
                 and 1 <= topk_group <= n_group
                 and topk_group * (E // n_group) >= K)
 
+    def _fused_route_ok(self, flat: torch.Tensor) -> bool:
+        """Prefill (more tokens than the fused gate takes) routes through
+        ops.moe_route: gate, stable expert sort and sub-ranges in HIP."""
+        n = flat.shape[0]
+        return (ops.use_native(flat) and ops.fused_route_enabled()
+                and n > 128 and n * self.top_k >= ops._MOE_GEMM_MIN_N
+                and self._fused_gate_ok(1))
+
     def packed_decode(self, n_tokens: int) -> bool:
         """True when forward() on n_tokens GPU tokens runs the packed
         fp16-dequant expert kernels (the consumers of an fp16 copy of
@@ -539,6 +550,18 @@ class DeepseekV2MoE(nn.Module):
                                           topk_group=topk_group,
                                           **self._gate_kwargs())
             y = self.switch_mlp.forward_subs(flat, subs, mt)
+        elif self._fused_route_ok(flat):
+            logits = self.gate(flat.to(self.gate.weight.dtype))
+            n_group, topk_group = self._gate_groups()
+            # weights rounded to the model dtype, as the torch route's
+            # w.to(x.dtype) below hands them to the experts
+            route = ops.moe_route(
+                logits, self.top_k, n_group, topk_group,
+                self.routed_scaling_factor, self.norm_topk_prob,
+                max_tok=ops.moe_route_max_tok(self.switch_mlp._fp8),
+                wt_bf16=x.dtype == torch.bfloat16, **self._gate_kwargs())
+            y = self.switch_mlp(flat, route.weights, route.indices,
+                                route=route)
         else:
             logits = self.gate(flat.to(self.gate.weight.dtype)).float()
             n_group, topk_group = self._gate_groups()

@@ -519,16 +519,22 @@ def _cached_gu_t(gate_w: torch.Tensor, up_w: torch.Tensor) -> torch.Tensor:
 
 
 def _moe_prefill_gemm(x, gate_w, up_w, down_w, weights, indices,
-                      dequant_all=None):
+                      dequant_all=None, route=None):
     """Large-N path: expert-padded batched GEMMs (hipBLASLt bmm).
 
     Tokens are scattered into an [E, cap, H] padded tensor (cap = max
     tokens on one expert) so the whole MoE layer is 3 bmm launches —
     a per-expert python GEMM loop costs ~400 host-side launches per
-    layer and made prefill host-bound."""
+    layer and made prefill host-bound.
+
+    route (ops.moe_route's result for these tokens) replaces the sort
+    below with its sorted arrays."""
     N, K = indices.shape
     H = x.shape[-1]
     dev = x.device
+    if route is not None:
+        return _moe_prefill_gemm_routed(x, gate_w, up_w, down_w, dequant_all,
+                                        route)
     flat_e = indices.reshape(-1).long()
     order = torch.argsort(flat_e, stable=True)
     sorted_e = flat_e[order]
@@ -579,6 +585,38 @@ def _moe_prefill_gemm(x, gate_w, up_w, down_w, weights, indices,
     return out.to(x.dtype)
 
 
+def _moe_prefill_gemm_routed(x, gate_w, up_w, down_w, dequant_all, route):
+    """_moe_prefill_gemm from a fused route: no argsort, bincount,
+    scatter_add, cumsum or inverse permutation.  Sorted position p of
+    expert e sits at padded row p + (e * cap - starts[e])."""
+    N, K = route.indices.shape
+    H = x.shape[-1]
+    dev = x.device
+    if H % 4 != 0:
+        raise ValueError("routed MoE prefill needs hidden % 4 == 0 "
+                         f"(got {H})")
+    ext = _require_ext("grouped_expert_mlp")
+    if dequant_all is not None:
+        gate_w, up_w, down_w = dequant_all()
+    E = gate_w.shape[0]
+    # the one host sync per layer this route already had (it sizes the
+    # padded tensor); it stays
+    cap = (int(route.max_count) + 127) // 128 * 128
+    shift = torch.arange(E, device=dev, dtype=torch.int32) * cap \
+        - route.starts[:E]
+    dst = torch.arange(N * K, device=dev, dtype=torch.int32) \
+        + shift[route.sorted_e]
+    pair_pos = route.pair_pos + shift[route.indices]
+    xp = x.new_zeros(E * cap, H)
+    ext.moe_scatter_rows(x, xp, route.sorted_tok, dst)
+    xp = xp.view(E, cap, H)
+    I = gate_w.shape[1]
+    gu = torch.bmm(xp, _cached_gu_t(gate_w, up_w))
+    hh = swiglu(gu[..., :I], gu[..., I:])
+    d = torch.bmm(hh, _cached_t(down_w)).reshape(E * cap, H)
+    return ext.moe_gather_reduce(d, pair_pos, route.weights, N)
+
+
 def moe_gate_subranges(router_logits_bf16, top_k: int,
                        routed_scaling_factor: float = 1.0,
                        norm_topk_prob: bool = False, max_tok: int = 4,
@@ -600,6 +638,47 @@ def moe_gate_subranges(router_logits_bf16, top_k: int,
                                         max_tok, routed_scaling_factor,
                                         norm_topk_prob, n_group, topk_group,
                                         scoring, e_bias))
+
+
+MoeRoute = ref.MoeRoute
+
+
+def fused_route_enabled() -> bool:
+    """Prefill MoE layers route through ops.moe_route (moe_route.hip).
+    MLXS_AMD_NO_FUSED_ROUTE=1 keeps the torch gate and sort for A/B in one
+    build."""
+    return not os.environ.get("MLXS_AMD_NO_FUSED_ROUTE")
+
+
+def moe_route_max_tok(fp8: bool) -> int:
+    """Sub-range size a prefill route is built for: the wide kernels' tile
+    for packed FP8 experts, 16 otherwise."""
+    if fp8:
+        return _require_ext("moe_route").moe_fp8f16_wide_tile()
+    return 16
+
+
+def moe_route(router_logits, top_k: int, n_group: int = 1,
+              topk_group: int = 1, routed_scaling_factor: float = 1.0,
+              norm_topk_prob: bool = False, max_tok: int = 16, *,
+              scoring: str = "softmax", e_bias=None,
+              wt_bf16: bool = False) -> MoeRoute:
+    """Gate + stable sort by expert + sub-range build for any token count:
+    reference.moe_route semantics, three kernel launches on GPU (bf16
+    logits; no host sync, graph-capturable).
+
+    Limits on GPU (the binding raises outside them): 1<=N<=262144 tokens,
+    E<=256 experts, k<=8, max_tok>=1 and the group limits of
+    moe_gate_subranges."""
+    if _use_hip(router_logits):
+        ext = _require_ext("moe_route")
+        return MoeRoute(*ext.moe_route(router_logits, top_k, max_tok,
+                                       routed_scaling_factor, norm_topk_prob,
+                                       n_group, topk_group, scoring, e_bias,
+                                       wt_bf16), max_tok)
+    return ref.moe_route(router_logits, top_k, n_group, topk_group,
+                         routed_scaling_factor, norm_topk_prob, max_tok,
+                         scoring=scoring, e_bias=e_bias, wt_bf16=wt_bf16)
 
 
 def moe_finalize(acc, shared, h):
@@ -718,11 +797,15 @@ def grouped_expert_mlp_quant_subs(x, gate, up, down, subs,
     return out.to(x.dtype)
 
 
-def grouped_expert_mlp(x, gate_w, up_w, down_w, weights, indices):
+def grouped_expert_mlp(x, gate_w, up_w, down_w, weights, indices, route=None):
+    """route: ops.moe_route's result for these tokens (weights and indices
+    are then its fields); the prefill route takes its sort from it, the
+    smaller shapes and the CPU do not look at it."""
     if _use_hip(x):
         _require_ext("grouped_expert_mlp")
         if x.shape[0] * indices.shape[1] >= _MOE_GEMM_MIN_N:
-            return _moe_prefill_gemm(x, gate_w, up_w, down_w, weights, indices)
+            return _moe_prefill_gemm(x, gate_w, up_w, down_w, weights, indices,
+                                     route=route)
         E = gate_w.shape[0]
         sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt, _ = \
             make_expert_subranges(indices, weights, E, max_tok=4)
@@ -779,9 +862,10 @@ def expert_dequant_resident(gate, up, down, group_size: int, bits: int):
 
 
 def grouped_expert_mlp_quant(x, gate, up, down, weights, indices,
-                             group_size: int, bits: int):
+                             group_size: int, bits: int, route=None):
     """Quantized stacked experts: gate/up/down are (w_q, scales, biases)
-    triplets with stacked [E, ...] layout."""
+    triplets with stacked [E, ...] layout.  route: as in
+    grouped_expert_mlp."""
     if _use_hip(x):
         _require_ext("grouped_expert_mlp_quant")
         E = gate[0].shape[0]
@@ -789,7 +873,8 @@ def grouped_expert_mlp_quant(x, gate, up, down, weights, indices,
             return _moe_prefill_gemm(
                 x, None, None, None, weights, indices,
                 dequant_all=lambda: expert_dequant(gate, up, down,
-                                                   group_size, bits))
+                                                   group_size, bits),
+                route=route)
         sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt, _ = \
             make_expert_subranges(indices, weights, E, max_tok=16)
         return grouped_expert_mlp_quant_subs(
@@ -898,14 +983,24 @@ def _fp8_prefill_route(pairs: int, resident: bool, kernel_ok: bool,
     return "dense" if resident else "packed"
 
 
-def _moe_prefill_fp8_packed(x, gate, up, down, weights, indices):
+def _moe_prefill_fp8_packed(x, gate, up, down, weights, indices, route=None):
     """Prefill from the packed e4m3 stacks: sub-ranges of the wide
     kernels' tile (device ops only, no host sync), fused gate+up+SiLU,
-    down with the routing-weighted fp32 scatter."""
+    down with the routing-weighted fp32 scatter.  A fused route brings
+    its sub-ranges along: no torch op runs in front of the kernels."""
     ext = _require_ext("grouped_expert_mlp_fp8")
-    sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt, _ = \
-        make_expert_subranges(indices, weights, gate[0].shape[0],
-                              max_tok=ext.moe_fp8f16_wide_tile())
+    if route is not None:
+        if route.max_tok != ext.moe_fp8f16_wide_tile():
+            raise ValueError(
+                "route built for %d-token sub-ranges, the wide kernels take "
+                "%d" % (route.max_tok, ext.moe_fp8f16_wide_tile()))
+        sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt = (
+            route.sub_expert, route.sub_off, route.sub_cnt, route.sorted_tok,
+            route.sorted_wt)
+    else:
+        sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt, _ = \
+            make_expert_subranges(indices, weights, gate[0].shape[0],
+                                  max_tok=ext.moe_fp8f16_wide_tile())
     hh = ext.moe_fp8f16_gateup_wide(
         _to_f16_cached(x), gate[0], up[0], gate[1], up[1], sub_e, sub_off,
         sub_cnt, sorted_tok, sorted_tok.shape[0])
@@ -914,10 +1009,11 @@ def _moe_prefill_fp8_packed(x, gate, up, down, weights, indices):
     return out.to(x.dtype)
 
 
-def grouped_expert_mlp_fp8(x, gate, up, down, weights, indices):
+def grouped_expert_mlp_fp8(x, gate, up, down, weights, indices, route=None):
     """FP8 block-quantized stacked experts: gate/up/down are
     (w8, weight_scale_inv) pairs with stacked [E, ...] layout.  On the
-    GPU the path is _fp8_prefill_route's."""
+    GPU the path is _fp8_prefill_route's.  route: as in
+    grouped_expert_mlp."""
     if _use_hip(x):
         _require_ext("grouped_expert_mlp_fp8")
         E = gate[0].shape[0]
@@ -930,15 +1026,16 @@ def grouped_expert_mlp_fp8(x, gate, up, down, weights, indices):
         resident = (env is None and kernel_ok and pairs >= _MOE_GEMM_MIN_N
                     and expert_dequant_fp8_resident(gate, up, down)
                     is not None)
-        route = _fp8_prefill_route(pairs, resident, kernel_ok, env)
-        if route == "packed":
+        path = _fp8_prefill_route(pairs, resident, kernel_ok, env)
+        if path == "packed":
             return _moe_prefill_fp8_packed(x, gate, up, down, weights,
-                                           indices)
-        if route == "dense":
+                                           indices, route)
+        if path == "dense":
             return _moe_prefill_gemm(
                 x, None, None, None, weights, indices,
                 dequant_all=lambda: tuple(
-                    t.to(x.dtype) for t in expert_dequant_fp8(gate, up, down)))
+                    t.to(x.dtype) for t in expert_dequant_fp8(gate, up, down)),
+                route=route)
         sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt, _ = \
             make_expert_subranges(indices, weights, E, max_tok=16)
         return grouped_expert_mlp_fp8_subs(

@@ -89,6 +89,10 @@ void launch_moe_w4_mfma(const void*, const void*, const void*, const void*,
 void launch_moe_gate_subranges(const void*, const float*, int, int*, float*,
                                int*, int*, int*, int, int, int, int, int,
                                float, int, int, int, hipStream_t);
+void launch_moe_route(const void*, const float*, int, int*, float*, int*, int*,
+                      int*, int*, int*, float*, int*, int*, int*, int*, int*,
+                      int, int, int, int, int, float, int, int, int, int,
+                      hipStream_t);
 void launch_moe_w4f16_gateup(const void*, const void*, const void*,
                              const void*, const void*, const void*,
                              const void*, void*, const int*, const int*,
@@ -1337,6 +1341,86 @@ std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
   return {sub_expert, sub_off, sub_cnt, sorted_tok, sorted_wt};
 }
 
+// Fused prefill routing (moe_route.hip): gate + stable expert sort +
+// sub-range build in three launches.  Returns indices, weights, counts,
+// starts, max_count, sorted_tok, sorted_wt, sorted_e, pair_pos, sub_expert,
+// sub_off, sub_cnt.  Nothing is zeroed and nothing syncs: safe under capture.
+std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t K,
+                                     int64_t max_tok, double routed_scaling,
+                                     bool norm_topk, int64_t n_group,
+                                     int64_t topk_group,
+                                     const std::string& scoring,
+                                     c10::optional<torch::Tensor> e_bias,
+                                     bool wt_bf16) {
+  check_bf16(logits, "logits");
+  TORCH_CHECK(scoring == "softmax" || scoring == "sigmoid",
+              "moe_route scoring must be 'softmax' or 'sigmoid' (got '",
+              scoring, "')");
+  const bool sigmoid = scoring == "sigmoid";
+  TORCH_CHECK(logits.dim() == 2, "logits must be [N, E]");
+  auto lc = logits.contiguous();
+  const int64_t N = lc.size(0), E = lc.size(1);
+  // the kernels' LDS arrays and int indices are sized for these limits
+  TORCH_CHECK(N >= 1 && N <= 262144 && E >= 1 && E <= 256 && K >= 1 && K <= 8,
+              "moe_route limits: 1<=N<=262144, 1<=E<=256, 1<=K<=8 (got N=", N,
+              ", E=", E, ", K=", K, ")");
+  TORCH_CHECK(n_group >= 1 && n_group <= 32 && E % n_group == 0,
+              "moe_route limits: 1<=n_group<=32 and E % n_group == 0 (got E=",
+              E, ", n_group=", n_group, ")");
+  TORCH_CHECK(topk_group >= 1 && topk_group <= n_group,
+              "moe_route limits: 1<=topk_group<=n_group (got topk_group=",
+              topk_group, ", n_group=", n_group, ")");
+  TORCH_CHECK(topk_group * (E / n_group) >= K,
+              "moe_route limits: topk_group*(E/n_group) >= K (got ",
+              topk_group, "*", E / n_group, " < ", K, ")");
+  TORCH_CHECK(max_tok >= 1, "moe_route needs max_tok >= 1");
+  // a sigmoid group is scored by its two best members
+  TORCH_CHECK(!sigmoid || n_group == 1 || E / n_group >= 2,
+              "moe_route limits: sigmoid scoring with groups needs "
+              "E/n_group >= 2 (got E=", E, ", n_group=", n_group, ")");
+  const float* bias_ptr = nullptr;
+  if (e_bias.has_value()) {
+    const torch::Tensor& eb = *e_bias;
+    TORCH_CHECK(sigmoid, "e_bias applies to sigmoid scoring only");
+    TORCH_CHECK(eb.scalar_type() == torch::kFloat32 && eb.is_contiguous() &&
+                    eb.device() == lc.device() && eb.dim() == 1 &&
+                    eb.size(0) == E,
+                "e_bias must be a contiguous fp32 [E] tensor on the logits' "
+                "device (E=", E, ")");
+    bias_ptr = eb.data_ptr<float>();
+  }
+  const int64_t P = N * K;
+  const int64_t s_upper = E + P / max_tok;
+  const int64_t nb = (N + 63) / 64;  // moe_route.hip: MR_TB tokens per block
+  auto io = torch::TensorOptions().dtype(torch::kInt32).device(lc.device());
+  auto fo = io.dtype(torch::kFloat32);
+  auto indices = torch::empty({N, K}, io);
+  auto weights = torch::empty({N, K}, fo);
+  auto blk_cnt = torch::empty({nb, E}, io);  // workspace
+  auto counts = torch::empty({E}, io);
+  auto starts = torch::empty({E + 1}, io);
+  auto max_count = torch::empty({1}, io);
+  auto sorted_tok = torch::empty({P}, io);
+  auto sorted_wt = torch::empty({P}, fo);
+  auto sorted_e = torch::empty({P}, io);
+  auto pair_pos = torch::empty({N, K}, io);
+  auto sub_expert = torch::empty({s_upper}, io);
+  auto sub_off = torch::empty({s_upper}, io);
+  auto sub_cnt = torch::empty({s_upper}, io);
+  launch_moe_route(
+      lc.data_ptr(), bias_ptr, sigmoid ? 1 : 0, indices.data_ptr<int>(),
+      weights.data_ptr<float>(), blk_cnt.data_ptr<int>(),
+      counts.data_ptr<int>(), starts.data_ptr<int>(),
+      max_count.data_ptr<int>(), sorted_tok.data_ptr<int>(),
+      sorted_wt.data_ptr<float>(), sorted_e.data_ptr<int>(),
+      pair_pos.data_ptr<int>(), sub_expert.data_ptr<int>(),
+      sub_off.data_ptr<int>(), sub_cnt.data_ptr<int>(), (int)N, (int)E, (int)K,
+      (int)s_upper, (int)max_tok, (float)routed_scaling, norm_topk ? 1 : 0,
+      (int)n_group, (int)topk_group, wt_bf16 ? 1 : 0, cur_stream());
+  return {indices, weights, counts, starts, max_count, sorted_tok, sorted_wt,
+          sorted_e, pair_pos, sub_expert, sub_off, sub_cnt};
+}
+
 // reference.sample_rows on device: edits logits in place, writes ids_out
 // and lse_out for the active rows.  No allocation: safe under capture.
 void sample_rows(torch::Tensor logits, torch::Tensor temperature,
@@ -1538,6 +1622,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("topk_group") = 1,
         pybind11::arg("scoring") = "softmax",
         pybind11::arg("e_bias") = pybind11::none());
+  m.def("moe_route", &moe_route, pybind11::arg("logits"),
+        pybind11::arg("top_k"), pybind11::arg("max_tok"),
+        pybind11::arg("routed_scaling"), pybind11::arg("norm_topk"),
+        pybind11::arg("n_group") = 1, pybind11::arg("topk_group") = 1,
+        pybind11::arg("scoring") = "softmax",
+        pybind11::arg("e_bias") = pybind11::none(),
+        pybind11::arg("wt_bf16") = false);
   m.def("moe_scatter_rows",
         [](torch::Tensor src, torch::Tensor dst, torch::Tensor src_idx,
            torch::Tensor dst_idx) {

@@ -13,7 +13,7 @@ MLX/mlx_lm; e.g. RMSNorm+RoPE via the blocks built at
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -378,6 +378,72 @@ def _moe_gate_sigmoid(router_logits, top_k, n_group, topk_group,
         weights = weights / (weights.sum(-1, keepdim=True) + 1e-20)
     weights = weights * routed_scaling_factor
     return weights, indices
+
+
+class MoeRoute(NamedTuple):
+    """A routed token batch: the gate's picks, their stable sort by expert
+    and the sub-range arrays of the grouped expert kernels.  Integer fields
+    are int32, weights fp32; P = N * K pairs, flat pair index n * K + k."""
+    indices: torch.Tensor     # [N, K] chosen experts, descending score
+    weights: torch.Tensor     # [N, K] after norm_topk and the routed scaling
+    counts: torch.Tensor      # [E] pairs per expert
+    starts: torch.Tensor      # [E + 1] exclusive prefix of counts
+    max_count: torch.Tensor   # [1] counts.max()
+    sorted_tok: torch.Tensor  # [P] token of each pair, sorted by expert
+    sorted_wt: torch.Tensor   # [P] its weight
+    sorted_e: torch.Tensor    # [P] its expert
+    pair_pos: torch.Tensor    # [N, K] sorted position of pair (n, k)
+    sub_expert: torch.Tensor  # [E + P // max_tok] see make_expert_subranges
+    sub_off: torch.Tensor
+    sub_cnt: torch.Tensor
+    max_tok: int
+
+
+def moe_route(router_logits: torch.Tensor, top_k: int, n_group: int = 1,
+              topk_group: int = 1, routed_scaling_factor: float = 1.0,
+              norm_topk_prob: bool = False, max_tok: int = 16, *,
+              scoring: str = "softmax", e_bias: Optional[torch.Tensor] = None,
+              wt_bf16: bool = False) -> MoeRoute:
+    """moe_gate, then the stable sort of the flat (token, k) pair list by
+    expert, then each expert's run cut into sub-ranges of <= max_tok pairs:
+    experts in order, an expert's slots contiguous, only its last one
+    partial, dead slots zeroed and last.  wt_bf16 rounds the weights to
+    bfloat16 (kept as fp32), what a bf16 model hands its experts."""
+    if max_tok < 1:
+        raise ValueError("moe_route: max_tok must be >= 1")
+    w, idx = moe_gate(router_logits, top_k, n_group, topk_group,
+                      routed_scaling_factor, norm_topk_prob, scoring=scoring,
+                      e_bias=e_bias)
+    w = w.float()
+    if wt_bf16:
+        w = w.to(torch.bfloat16).float()
+    N, K = idx.shape
+    E = router_logits.shape[-1]
+    P = N * K
+    dev = idx.device
+    i32 = torch.int32
+    flat_e = idx.reshape(-1)
+    order = torch.argsort(flat_e, stable=True)
+    counts = torch.bincount(flat_e, minlength=E)
+    starts = torch.zeros(E + 1, dtype=torch.int64, device=dev)
+    starts[1:] = torch.cumsum(counts, 0)
+    pair_pos = torch.empty(P, dtype=torch.int64, device=dev)
+    pair_pos[order] = torch.arange(P, device=dev)
+    nsub = (counts + max_tok - 1) // max_tok
+    live_e = torch.repeat_interleave(torch.arange(E, device=dev), nsub)
+    j = torch.arange(live_e.numel(), device=dev) \
+        - (torch.cumsum(nsub, 0) - nsub)[live_e]
+    s_upper = E + P // max_tok
+    subs = torch.zeros(3, s_upper, dtype=torch.int64, device=dev)
+    subs[0, :live_e.numel()] = live_e
+    subs[1, :live_e.numel()] = starts[live_e] + j * max_tok
+    subs[2, :live_e.numel()] = (counts[live_e] - j * max_tok).clamp(max=max_tok)
+    return MoeRoute(
+        idx.to(i32), w, counts.to(i32), starts.to(i32),
+        counts.max().reshape(1).to(i32), (order // K).to(i32),
+        w.reshape(-1)[order].contiguous(), flat_e[order].to(i32),
+        pair_pos.view(N, K).to(i32), subs[0].to(i32), subs[1].to(i32),
+        subs[2].to(i32), max_tok)
 
 
 def grouped_expert_mlp(x: torch.Tensor, gate_w: torch.Tensor, up_w: torch.Tensor,

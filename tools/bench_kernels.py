@@ -96,6 +96,67 @@ def bench_v3(ops, ext, dev="cuda"):
               f"~{kv_bytes / (med / 1e6) / 1e12:.2f} TB/s of one K pass")
 
 
+def bench_moe_route(ops, ref, dev="cuda", iters=200):
+    """The fused prefill routing (ops.moe_route, three launches) against the
+    torch sequences it replaces: ref.moe_gate on the GPU + the bf16 weight
+    cast, followed by make_expert_subranges (the packed route's prologue) or
+    by the sort section of _moe_prefill_gemm without its host sync (the
+    batched-GEMM route's).  The three alternate in one process after
+    warm-up, two rounds; median of five windows of `iters` calls between
+    device events, with min-max."""
+    shapes = [(E, K, ng, tg, sc, N) for (E, K, ng, tg, sc) in
+              ((64, 6, 1, 1, "softmax"), (256, 8, 8, 4, "sigmoid"))
+              for N in (512, 4096, 32768)]
+    g = torch.Generator().manual_seed(1)
+    for E, K, n_group, topk_group, scoring, N in shapes:
+        logits = torch.randn(N, E, generator=g).to(torch.bfloat16).to(dev)
+        kw = {}
+        if scoring == "sigmoid":
+            kw = {"scoring": "sigmoid",
+                  "e_bias": (torch.rand(E, generator=g) * 2.0 - 1.5).to(dev)}
+        norm, scaling, max_tok = scoring == "sigmoid", 2.5, 64
+
+        def fused():
+            return ops.moe_route(logits, K, n_group, topk_group, scaling,
+                                 norm, max_tok, wt_bf16=True, **kw)
+
+        def gate():
+            w, idx = ref.moe_gate(logits.float(), K, n_group, topk_group,
+                                  scaling, norm, **kw)
+            return w.to(torch.bfloat16), idx
+
+        def torch_subranges():
+            w, idx = gate()
+            return ops.make_expert_subranges(idx, w, E, max_tok=max_tok)
+
+        def torch_gemm_sort():
+            # _moe_prefill_gemm up to its scatter, cap fixed (no host sync)
+            w, idx = gate()
+            cap = N
+            flat_e = idx.reshape(-1).long()
+            order = torch.argsort(flat_e, stable=True)
+            sorted_e = flat_e[order]
+            tok = torch.arange(N, device=dev).repeat_interleave(K)[order]
+            counts = torch.zeros(E, dtype=torch.long, device=dev)
+            counts.scatter_add_(0, sorted_e, torch.ones_like(sorted_e))
+            start = torch.cumsum(counts, 0) - counts
+            dst = sorted_e * cap + torch.arange(N * K, device=dev) \
+                - start[sorted_e]
+            inv = torch.empty_like(order)
+            inv[order] = torch.arange(N * K, device=dev)
+            return (tok.to(torch.int32), dst.to(torch.int32),
+                    dst[inv].view(N, K).to(torch.int32), w.float())
+
+        for rnd in range(2):
+            for name, fn in (("fused", fused),
+                             ("torch+subranges", torch_subranges),
+                             ("torch+gemm-sort", torch_gemm_sort)):
+                med, lo, hi = _repeat(fn, iters)
+                print(f"moe_route N={N:5d} E={E:3d} k={K} {scoring:7s} "
+                      f"{name:15s} round {rnd}: median {med:8.1f} us  "
+                      f"min {lo:8.1f}  max {hi:8.1f}", flush=True)
+
+
 # vendor-published MI355X peaks, for the share-of-bound column
 _PEAK_HBM = 8.0e12        # B/s
 _PEAK_BF16 = 2.5e15       # dense bf16 matrix FLOP/s
@@ -463,6 +524,9 @@ def main():
     ap.add_argument("--mla-chunk", action="store_true",
                     help="only the short-chunk-over-a-prefix comparison: "
                          "expanded prefill vs the absorbed mla_chunk path")
+    ap.add_argument("--moe-route", action="store_true",
+                    help="only the prefill routing comparison: the fused "
+                         "moe_route kernels vs the torch gate + sort")
     args = ap.parse_args()
     from mlx_sharding_amd import ops
     from mlx_sharding_amd.ops import reference as ref
@@ -471,6 +535,9 @@ def main():
     dev = "cuda"
     torch.manual_seed(0)
 
+    if args.moe_route:
+        bench_moe_route(ops, ref, dev)
+        return
     if args.mla_only:
         bench_mla(ops, ext, dev)
         return
