@@ -234,12 +234,16 @@ class MLAAttention(nn.Module):
                 and dk % 8 == 0 and self.kv_lora_rank % 8 == 0
                 and ext.attn_decode_shape_ok(self.n_heads, self.kv_lora_rank))
 
-    def _mla_mfma(self, x) -> bool:
-        """T == 1 absorbed attention goes to the MFMA kernel: native
-        path, a shape it serves (32 / 64 / 128 heads), not switched off."""
+    def _mla_mfma(self, x, k_all, gp) -> bool:
+        """T == 1 absorbed attention over the cache view k_all (the whole
+        capacity buffer under a device position gp) goes to the MFMA
+        kernel: native path, a shape, batch and key span it is routed for
+        (ops.mla_decode_route: 32 / 64 / 128 heads, 16 heads at batch >= 64
+        over long spans), not switched off."""
         return (ops.use_native(x) and ops.mla_decode_enabled()
-                and ops.mla_decode_shape_ok(self.n_heads, self.kv_lora_rank,
-                                            self.qk_rope))
+                and ops.mla_decode_route(self.n_heads, self.kv_lora_rank,
+                                         self.qk_rope, x.shape[0],
+                                         k_all.shape[2], gp is not None))
 
     def _ensure_absorb(self, device, dtype):
         if self._w_uk is not None:
@@ -320,7 +324,7 @@ class MLAAttention(nn.Module):
             # q absorb: [nh, B, nope] @ [nh, nope, rank] -> [nh, B, rank]
             qn = q_nope.permute(2, 0, 1, 3).reshape(nh, B * T, self.qk_nope)
             q_abs = torch.bmm(qn, self._w_uk)           # [nh, B, rank]
-            if self._mla_mfma(x):
+            if self._mla_mfma(x, k_all, gp):
                 o = ops.mla_decode(q_abs.transpose(0, 1), q_pe[:, 0], k_all,
                                    rank, self.scale, gp)    # [nh, B, rank]
             else:
@@ -391,7 +395,7 @@ class MLAAttention(nn.Module):
             self.qk_rope)
         self._ensure_absorb(qh.device, qh.dtype)
         q_abs = torch.bmm(qn, self._w_uk)               # [nh, B, rank]
-        if self._mla_mfma(qh):
+        if self._mla_mfma(qh, k_all, gp):
             o = ops.mla_decode(q_abs.transpose(0, 1), q_pe, k_all, rank,
                                self.scale, gp)          # [nh, B, rank]
         else:

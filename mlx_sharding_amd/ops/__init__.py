@@ -175,6 +175,28 @@ def mla_decode_shape_ok(n_heads: int, rank: int, rope: int) -> bool:
                                                        rank)
 
 
+def mla_decode_route(n_heads: int, rank: int, rope: int, batch: int,
+                     span: int, device_pos: bool) -> bool:
+    """True when T == 1 absorbed attention of this shape should take the
+    MFMA kernel.  ``span`` is the key extent of the cache view: the row
+    length with a host-side length, the whole capacity buffer under a
+    device position (``device_pos``), where the row's length is not known
+    on the host.  32 / 64 / 128 heads always do.  At 16 heads over the
+    (576, 512) rows the kernel was measured against attn_decode_split
+    (PERFORMANCE.md) and is routed only where it won every measured row:
+    batch >= 64 with a host-side length >= 1024, and batch >= 64 under a
+    device position over a capacity >= 4096 (it won at every length from
+    256 keys to the capacity).  At batch 1 and 16 under a device position
+    it lost at short lengths, so smaller batches stay on the head-group
+    kernel, as does everything not measured.  The (80, 64) debug rows were
+    run for correctness only and always take it."""
+    if not mla_decode_shape_ok(n_heads, rank, rope):
+        return False
+    if n_heads != 16 or rank != 512:
+        return True
+    return batch >= 64 and span >= (4096 if device_pos else 1024)
+
+
 def mla_decode(q_nope, q_rope, kv, rank: int, scale: float, pos_dev=None):
     """Absorbed-MLA decode attention (T == 1, one KV head) over the
     compressed cache.

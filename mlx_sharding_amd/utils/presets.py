@@ -223,6 +223,13 @@ PRESETS["debug-deepseek-grouped"] = dict(
     norm_topk_prob=False,
 )
 
+# debug-deepseek with DeepSeek-V2-Lite's 16 heads over rows (80, 64): the
+# 16-head MFMA decode kernel (mla_decode16_kernel)
+PRESETS["debug-deepseek-h16"] = dict(
+    PRESETS["debug-deepseek"],
+    num_attention_heads=16,
+)
+
 # debug-deepseek as a DeepSeek-V3: sigmoid router with a selection bias
 # over 96 experts in 8 groups (more than one register row in the fused
 # gate), a q_lora_rank, and 32 heads (the head-group decode path)

@@ -163,42 +163,52 @@ _PEAK_BF16 = 2.5e15       # dense bf16 matrix FLOP/s
 
 
 def bench_mla(ops, ext, dev="cuda", iters=200):
-    """Absorbed MLA decode at B=64, Hq=128, Dk=576, Dv=512: the head-group
-    attn_decode_split kernel and the MFMA mla_decode kernel, alternated in
-    one process after warm-up, with a host-side S and with a device [B]
-    position over a capacity-S buffer.  Median of five windows between
-    device events (min-max).  The bound is the larger of the one-pass KV
-    bytes over peak HBM bandwidth and the QK+PV FLOPs over peak bf16."""
-    B, Hq, Dk, Dv = 64, 128, 576, 512
+    """Absorbed MLA decode, Dk=576, Dv=512: the head-group attn_decode_split
+    kernel and the MFMA mla_decode kernel, alternated in one process after
+    warm-up.  Rows are (B, Hq, S, mode, L): "host" passes S on the host,
+    "device" passes an int32 [B] position L - 1 over a capacity-S buffer.
+    128 heads at B=64, S=512/4096, both modes; 16 heads at B=64,
+    S=512/1024/2048/4096, both modes, and at B=1, S=1024/4096, device, all
+    with L = S; and the serving case, 16 heads under a device position with
+    L far below a 4096-key capacity (L=256/512/1024 at B=1/16/64).  Median
+    of five windows between device events (min-max).  The bound is the
+    larger of the one-pass bytes of the L live KV rows over peak HBM
+    bandwidth and the QK+PV FLOPs over peak bf16."""
+    Dk, Dv = 576, 512
     scale = Dk ** -0.5
-    q_abs = torch.randn(Hq, B, Dv, dtype=torch.bfloat16, device=dev)
-    q_pe = torch.randn(B, Hq, Dk - Dv, dtype=torch.bfloat16, device=dev)
-    qn = q_abs.transpose(0, 1)
-    for S in (512, 4096):
+    rows = [(64, 128, S, m, S) for S in (512, 4096) for m in ("host", "device")]
+    rows += [(64, 16, S, m, S) for S in (512, 1024, 2048, 4096)
+             for m in ("host", "device")]
+    rows += [(1, 16, S, "device", S) for S in (1024, 4096)]
+    rows += [(B, 16, 4096, "device", L) for B in (1, 16, 64)
+             for L in (256, 512, 1024)]
+    for B, Hq, S, mode, L in rows:
+        q_abs = torch.randn(Hq, B, Dv, dtype=torch.bfloat16, device=dev)
+        q_pe = torch.randn(B, Hq, Dk - Dv, dtype=torch.bfloat16, device=dev)
+        qn = q_abs.transpose(0, 1)
         kv = torch.randn(B, 1, S, Dk, dtype=torch.bfloat16, device=dev) * 0.5
         v = kv[..., :Dv]
-        nbytes = B * S * Dk * 2
-        flops = 2 * B * Hq * S * (Dk + Dv)
+        nbytes = B * L * Dk * 2
+        flops = 2 * B * Hq * L * (Dk + Dv)
         t_mem, t_mma = nbytes / _PEAK_HBM * 1e6, flops / _PEAK_BF16 * 1e6
         bound, which = max((t_mem, "HBM"), (t_mma, "MFMA"))
-        for mode in ("host", "device"):
-            pos = None if mode == "host" else torch.full(
-                (B,), S - 1, dtype=torch.int32, device=dev)
-            fns = (("attn_decode_split", lambda: ext.attn_decode_split(
-                        qn, q_pe, kv, v, scale, 0.0, 0, pos)),
-                   ("mla_decode", lambda: ext.mla_decode(
-                        qn, q_pe, kv, Dv, scale, pos)))
-            diff = (fns[0][1]().float() - fns[1][1]().float()).abs().max()
-            print(f"S={S} {mode}: max |old - new| = {diff.item():.3e}, "
-                  f"mla_decode_nsplit = "
-                  f"{ext.mla_decode_nsplit(B, Hq, S)}")
-            for rnd in range(2):  # alternate the two kernels
-                for name, fn in fns:
-                    med, lo, hi = _repeat(fn, iters)
-                    print(f"{name:18s} S={S:5d} {mode:6s} round {rnd}: "
-                          f"median {med:8.1f} us  min {lo:8.1f}  "
-                          f"max {hi:8.1f}  bound {bound:5.1f} us ({which}) "
-                          f"-> {100 * bound / med:5.1f}%")
+        pos = None if mode == "host" else torch.full(
+            (B,), L - 1, dtype=torch.int32, device=dev)
+        fns = (("attn_decode_split", lambda: ext.attn_decode_split(
+                    qn, q_pe, kv, v, scale, 0.0, 0, pos)),
+               ("mla_decode", lambda: ext.mla_decode(
+                    qn, q_pe, kv, Dv, scale, pos)))
+        diff = (fns[0][1]().float() - fns[1][1]().float()).abs().max()
+        tag = f"B={B:2d} Hq={Hq:3d} S={S:5d} {mode:6s} L={L:5d}"
+        print(f"{tag}: max |old - new| = {diff.item():.3e}, "
+              f"mla_decode_nsplit = {ext.mla_decode_nsplit(B, Hq, S)}")
+        for rnd in range(2):  # alternate the two kernels
+            for name, fn in fns:
+                med, lo, hi = _repeat(fn, iters)
+                print(f"{name:18s} {tag} round {rnd}: median {med:8.1f} us  "
+                      f"min {lo:8.1f}  max {hi:8.1f}  "
+                      f"bound {bound:5.2f} us ({which}) "
+                      f"-> {100 * bound / med:5.1f}%", flush=True)
 
 
 def bench_mla_chunk(ops, ext, dev="cuda", iters=200):
@@ -519,8 +529,9 @@ def main():
                     help="only the DeepSeek-V3 gate and 128-head attention "
                          "lines")
     ap.add_argument("--mla-only", action="store_true",
-                    help="only the 128-head absorbed-MLA decode comparison: "
-                         "attn_decode_split vs the MFMA mla_decode kernel")
+                    help="only the 128- and 16-head absorbed-MLA decode "
+                         "comparison: attn_decode_split vs the MFMA "
+                         "mla_decode kernels")
     ap.add_argument("--mla-chunk", action="store_true",
                     help="only the short-chunk-over-a-prefix comparison: "
                          "expanded prefill vs the absorbed mla_chunk path")
