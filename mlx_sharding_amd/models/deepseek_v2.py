@@ -562,7 +562,9 @@ class DeepseekV2MoE(nn.Module):
             route = ops.moe_route(
                 logits, self.top_k, n_group, topk_group,
                 self.routed_scaling_factor, self.norm_topk_prob,
-                max_tok=ops.moe_route_max_tok(self.switch_mlp._fp8),
+                max_tok=ops.moe_route_max_tok(
+                    self.switch_mlp._fp8,
+                    affine=self.switch_mlp.quant is not None),
                 wt_bf16=x.dtype == torch.bfloat16, **self._gate_kwargs())
             y = self.switch_mlp(flat, route.weights, route.indices,
                                 route=route)

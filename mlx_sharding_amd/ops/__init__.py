@@ -672,11 +672,14 @@ def fused_route_enabled() -> bool:
     return not os.environ.get("MLXS_AMD_NO_FUSED_ROUTE")
 
 
-def moe_route_max_tok(fp8: bool) -> int:
+def moe_route_max_tok(fp8: bool, affine: bool = False) -> int:
     """Sub-range size a prefill route is built for: the wide kernels' tile
-    for packed FP8 experts, 16 otherwise."""
+    for packed FP8 experts and for affine-quantized (w4/w8) experts, 16
+    otherwise.  The batched-GEMM route does not read the sub-ranges."""
     if fp8:
         return _require_ext("moe_route").moe_fp8f16_wide_tile()
+    if affine:
+        return _require_ext("moe_route").moe_w4f16_wide_tile()
     return 16
 
 
@@ -883,15 +886,101 @@ def expert_dequant_resident(gate, up, down, group_size: int, bits: int):
     return res if getattr(gate[0], "_mlxs_dq", None) is not None else None
 
 
+_W4_PREFILL_ENV = "MLXS_AMD_W4_PREFILL"
+
+
+def _w4_prefill_env() -> Optional[str]:
+    return os.environ.get(_W4_PREFILL_ENV) or None
+
+
+def _w4_kernel_ok(gate, up, down, group_size: int, bits: int) -> bool:
+    """The w4_prefill.hip kernels' preconditions: 4/8 bits, group size
+    32/64/128, both reduction dimensions multiples of 128, contiguous
+    stacks."""
+    if bits not in (4, 8) or group_size not in (32, 64, 128):
+        return False
+    pw = 32 // bits
+    return (gate[0].shape[-1] * pw % 128 == 0
+            and down[0].shape[-1] * pw % 128 == 0
+            and all(t.is_contiguous() for m in (gate, up, down) for t in m))
+
+
+def _w4_prefill_route(pairs: int, resident: bool, kernel_ok: bool,
+                      env: Optional[str]) -> str:
+    """Which path a GPU grouped_expert_mlp_quant call takes
+    (_fp8_prefill_route's truth table):
+
+    "tiles16" — the 16-token packed kernels (under _MOE_GEMM_MIN_N pairs);
+    "dense"   — _moe_prefill_gemm on the dense bf16 triplet, resident in
+                the dq-cache or dequantized for this call;
+    "packed"  — the wide-tile packed kernels (w4_prefill.hip).
+
+    resident: expert_dequant_resident has a dense triplet (only asked for
+    when env is unset).  kernel_ok: _w4_kernel_ok.  env:
+    MLXS_AMD_W4_PREFILL, None when unset."""
+    if env not in (None, "packed", "dense"):
+        raise ValueError("%s must be 'packed' or 'dense' (got %r)"
+                         % (_W4_PREFILL_ENV, env))
+    if pairs < _MOE_GEMM_MIN_N:
+        return "tiles16"
+    if env == "dense" or not kernel_ok:
+        return "dense"
+    if env == "packed":
+        return "packed"
+    return "dense" if resident else "packed"
+
+
+def _moe_prefill_w4_packed(x, gate, up, down, weights, indices,
+                           group_size: int, bits: int, route=None):
+    """Prefill from the packed w4/w8 stacks: sub-ranges of the wide
+    kernels' tile (device ops only, no host sync), fused gate+up+SiLU,
+    down with the routing-weighted fp32 scatter.  A fused route brings
+    its sub-ranges along: no torch op runs in front of the kernels."""
+    ext = _require_ext("grouped_expert_mlp_quant")
+    tile = ext.moe_w4f16_wide_tile()
+    if route is not None:
+        if route.max_tok != tile:
+            raise ValueError(
+                "route built for %d-token sub-ranges, the wide kernels take "
+                "%d" % (route.max_tok, tile))
+        sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt = (
+            route.sub_expert, route.sub_off, route.sub_cnt, route.sorted_tok,
+            route.sorted_wt)
+    else:
+        sub_e, sub_off, sub_cnt, sorted_tok, sorted_wt, _ = \
+            make_expert_subranges(indices, weights, gate[0].shape[0],
+                                  max_tok=tile)
+    hh = ext.moe_w4f16_gateup_wide(
+        _to_f16_cached(x), repack_w4(gate[0], bits), repack_w4(up[0], bits),
+        gate[1], gate[2], up[1], up[2], sub_e, sub_off, sub_cnt, sorted_tok,
+        sorted_tok.shape[0], group_size, bits)
+    out = ext.moe_w4f16_down_wide(
+        hh, repack_w4(down[0], bits), down[1], down[2], sub_e, sub_off,
+        sub_cnt, sorted_tok, sorted_wt, x.shape[0], group_size, bits)
+    return out.to(x.dtype)
+
+
 def grouped_expert_mlp_quant(x, gate, up, down, weights, indices,
                              group_size: int, bits: int, route=None):
     """Quantized stacked experts: gate/up/down are (w_q, scales, biases)
-    triplets with stacked [E, ...] layout.  route: as in
-    grouped_expert_mlp."""
+    triplets with stacked [E, ...] layout.  On the GPU the path is
+    _w4_prefill_route's.  route: as in grouped_expert_mlp."""
     if _use_hip(x):
         _require_ext("grouped_expert_mlp_quant")
         E = gate[0].shape[0]
-        if indices.numel() >= _MOE_GEMM_MIN_N:
+        env = _w4_prefill_env()
+        pairs = indices.numel()
+        kernel_ok = _w4_kernel_ok(gate, up, down, group_size, bits)
+        # the resident lookup builds the dense copy when the budget admits
+        # it: only ask where the answer decides the route
+        resident = (env is None and kernel_ok and pairs >= _MOE_GEMM_MIN_N
+                    and expert_dequant_resident(gate, up, down, group_size,
+                                                bits) is not None)
+        path = _w4_prefill_route(pairs, resident, kernel_ok, env)
+        if path == "packed":
+            return _moe_prefill_w4_packed(x, gate, up, down, weights, indices,
+                                          group_size, bits, route)
+        if path == "dense":
             return _moe_prefill_gemm(
                 x, None, None, None, weights, indices,
                 dequant_all=lambda: expert_dequant(gate, up, down,

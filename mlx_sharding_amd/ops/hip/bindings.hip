@@ -127,6 +127,17 @@ void launch_moe_fp8f16_down_wide(const void*, const void*, const float*,
                                  float*, const int*, const int*, const int*,
                                  const int*, const float*, int, int, int,
                                  hipStream_t);
+int moe_w4f16_wide_tile();
+void launch_moe_w4f16_gateup_wide(const void*, const void*, const void*,
+                                  const void*, const void*, const void*,
+                                  const void*, void*, const int*, const int*,
+                                  const int*, const int*, int, int, int, int,
+                                  int, hipStream_t);
+void launch_moe_w4f16_down_wide(const void*, const void*, const void*,
+                                const void*, float*, long, const int*,
+                                const int*, const int*, const int*,
+                                const float*, int, int, int, int, int,
+                                hipStream_t);
 void launch_sample_rows(float*, const float*, const float*, const float*,
                         const int*, long long*, long, float*, const int*,
                         const float*, int, const int*, const float*, int, int,
@@ -1278,6 +1289,109 @@ torch::Tensor moe_fp8f16_down_wide(torch::Tensor hh, torch::Tensor dw,
   return out;
 }
 
+// ---- w4/w8 prefill-regime pair (w4_prefill.hip) --------------------------
+// wq: repacked u32 words [E, O, K*bits/32] (ops.repack_w4); sc/bi: bf16
+// [E, O, K/gs].  K is the reduction dimension.
+void check_w4_wide(const torch::Tensor& wq, const torch::Tensor& sc,
+                   const torch::Tensor& bi, int64_t K, int64_t gs,
+                   int64_t bits, const char* op) {
+  TORCH_CHECK(bits == 4 || bits == 8, op, ": bits must be 4 or 8 (got ", bits,
+              ")");
+  TORCH_CHECK(gs == 32 || gs == 64 || gs == 128, op,
+              ": gs must be 32, 64 or 128 (got ", gs, ")");
+  TORCH_CHECK(K >= 128 && K % 128 == 0, op, " needs K % 128 == 0 (got K=", K,
+              ")");
+  TORCH_CHECK(wq.is_cuda() && sc.is_cuda() && bi.is_cuda(), op,
+              ": tensors must be on GPU");
+  TORCH_CHECK(wq.dim() == 3 && sc.dim() == 3 && bi.dim() == 3, op,
+              ": weight, scales and biases must be 3-d");
+  TORCH_CHECK(wq.element_size() == 4 && !wq.is_floating_point(), op,
+              ": weight must be packed 32-bit words");
+  TORCH_CHECK(sc.scalar_type() == torch::kBFloat16 &&
+                  bi.scalar_type() == torch::kBFloat16,
+              op, ": scales and biases must be bf16");
+  TORCH_CHECK(wq.is_contiguous() && sc.is_contiguous() && bi.is_contiguous(),
+              op, ": weight, scales and biases must be contiguous");
+  TORCH_CHECK(wq.size(0) >= 1 && wq.size(1) >= 1, op, ": empty weight");
+  TORCH_CHECK(wq.size(2) == K * bits / 32, op,
+              ": weight must be [E, O, K*bits/32] (K=", K, ")");
+  TORCH_CHECK(sc.size(0) == wq.size(0) && sc.size(1) == wq.size(1) &&
+                  sc.size(2) == K / gs && bi.sizes() == sc.sizes(),
+              op, ": scales and biases must be [E, O, K/gs]");
+  // the kernels read a lane's words of a k-block as 16-byte vectors
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0, op,
+              ": weight must be 16-byte aligned");
+}
+
+// Fused gate+up+SiLU over sub-ranges built for moe_w4f16_wide_tile()
+// tokens.  x [N, H] fp16; returns h [P, I] fp16.
+torch::Tensor moe_w4f16_gateup_wide(torch::Tensor x, torch::Tensor gq,
+                                    torch::Tensor uq, torch::Tensor gsc,
+                                    torch::Tensor gbi, torch::Tensor usc,
+                                    torch::Tensor ubi,
+                                    torch::Tensor sub_expert,
+                                    torch::Tensor sub_off,
+                                    torch::Tensor sub_cnt,
+                                    torch::Tensor sorted_tok, int64_t P,
+                                    int64_t gs, int64_t bits) {
+  const char* op = "moe_w4f16_gateup_wide";
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kHalf && x.dim() == 2 &&
+                  x.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              op, ": x must be contiguous 16-byte aligned fp16 [N, H] on GPU");
+  const int64_t H = x.size(1);
+  check_w4_wide(gq, gsc, gbi, H, gs, bits, op);
+  check_w4_wide(uq, usc, ubi, H, gs, bits, op);
+  check_subranges(sub_expert, sub_off, sub_cnt, sorted_tok, op);
+  TORCH_CHECK(gq.sizes() == uq.sizes(), op, ": gate/up shape mismatch");
+  TORCH_CHECK(P == sorted_tok.size(0), op, ": P must be len(sorted_tok)");
+  const int I = gq.size(1);
+  const int S = sub_expert.size(0);
+  auto h = torch::empty({P, I}, x.options());
+  launch_moe_w4f16_gateup_wide(
+      x.data_ptr(), gq.data_ptr(), uq.data_ptr(), gsc.data_ptr(),
+      gbi.data_ptr(), usc.data_ptr(), ubi.data_ptr(), h.data_ptr(),
+      sub_expert.data_ptr<int>(), sub_off.data_ptr<int>(),
+      sub_cnt.data_ptr<int>(), sorted_tok.data_ptr<int>(), S, (int)H, I,
+      (int)gs, (int)bits, cur_stream());
+  return h;
+}
+
+// hh [P, I] fp16; returns fp32 [N, H], zeroed by a kernel of the launch.
+torch::Tensor moe_w4f16_down_wide(torch::Tensor hh, torch::Tensor dq,
+                                  torch::Tensor dsc, torch::Tensor dbi,
+                                  torch::Tensor sub_expert,
+                                  torch::Tensor sub_off, torch::Tensor sub_cnt,
+                                  torch::Tensor sorted_tok,
+                                  torch::Tensor sorted_wt, int64_t N,
+                                  int64_t gs, int64_t bits) {
+  const char* op = "moe_w4f16_down_wide";
+  TORCH_CHECK(hh.is_cuda() && hh.scalar_type() == torch::kHalf &&
+                  hh.dim() == 2 && hh.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(hh.data_ptr()) % 16 == 0,
+              op, ": h must be contiguous 16-byte aligned fp16 [P, I] on GPU");
+  const int64_t I = hh.size(1);
+  check_w4_wide(dq, dsc, dbi, I, gs, bits, op);
+  check_subranges(sub_expert, sub_off, sub_cnt, sorted_tok, op);
+  TORCH_CHECK(hh.size(0) == sorted_tok.size(0), op,
+              ": P must be len(sorted_tok)");
+  TORCH_CHECK(sorted_wt.scalar_type() == torch::kFloat32 &&
+                  sorted_wt.is_contiguous() &&
+                  sorted_wt.size(0) == sorted_tok.size(0),
+              op, ": sorted_wt must be fp32 and match sorted_tok");
+  TORCH_CHECK(N >= 1, op, ": N must be positive");
+  const int H = dq.size(1);
+  const int S = sub_expert.size(0);
+  auto out = torch::empty({N, H}, hh.options().dtype(torch::kFloat32));
+  launch_moe_w4f16_down_wide(
+      hh.data_ptr(), dq.data_ptr(), dsc.data_ptr(), dbi.data_ptr(),
+      out.data_ptr<float>(), (long)out.numel(), sub_expert.data_ptr<int>(),
+      sub_off.data_ptr<int>(), sub_cnt.data_ptr<int>(),
+      sorted_tok.data_ptr<int>(), sorted_wt.data_ptr<float>(), S, (int)I, H,
+      (int)gs, (int)bits, cur_stream());
+  return out;
+}
+
 std::vector<torch::Tensor> moe_gate_subranges(torch::Tensor logits, int64_t K,
                                               int64_t s_upper, int64_t max_tok,
                                               double routed_scaling,
@@ -1615,6 +1729,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_fp8f16_gateup_wide", &moe_fp8f16_gateup_wide);
   m.def("moe_fp8f16_down_wide", &moe_fp8f16_down_wide);
   m.def("moe_fp8f16_wide_tile", []() { return moe_fp8f16_wide_tile(); });
+  m.def("moe_w4f16_gateup_wide", &moe_w4f16_gateup_wide);
+  m.def("moe_w4f16_down_wide", &moe_w4f16_down_wide);
+  m.def("moe_w4f16_wide_tile", []() { return moe_w4f16_wide_tile(); });
   m.def("moe_gate_subranges", &moe_gate_subranges, pybind11::arg("logits"),
         pybind11::arg("top_k"), pybind11::arg("s_upper"),
         pybind11::arg("max_tok"), pybind11::arg("routed_scaling"),

@@ -11,18 +11,9 @@
 // column tiles, so an expert's weights are read once per F8W_TM tokens.
 //
 // The activations ARE shared by the four waves: the F8W_TM x 128 fp16 slab
-// of a k-block is gathered once per block into LDS in full 256-byte
-// rows (16 lanes per row), double-buffered, one barrier per k-block, and
-// read back as 16-byte B fragments.  LDS image, in 16-byte slots:
-//     slot(t, c) = c * F8W_TM + (t ^ swz(c)),   c = k / 8 in 0..15,
-//     swz(c) = ((c & 3) << 1) | ((c >> 2) & 1)
-// A fragment read has c = q * 4 + i (lane quarter q, MFMA i): the 16 lanes
-// of a ds_read_b128 group hold two quarters q, q + 1 with complementary
-// token sets ({0-3, 12-15} and {4-11}); F8W_TM * 16 bytes is a multiple of
-// the 256-byte bank row, swz differs between the two only in bit 0 and both
-// sets are closed under that, so the group covers 16 distinct slots.  A
-// gather write has 8 consecutive lanes on one token and c = 0..7 (or
-// 8..15), where swz takes 8 distinct values: no bank is hit twice.
+// of a k-block is gathered once per block into LDS, double-buffered, one
+// barrier per k-block, and read back as 16-byte B fragments (geometry and
+// bank argument in wide_slab.h).
 //
 // Token rows past cnt are clamped for loads and masked for stores; token
 // column tiles wholly past cnt skip their MFMAs.  There are barriers
@@ -36,6 +27,7 @@
 
 #include "hip_common.h"
 #include "fp8_block.h"
+#include "wide_slab.h"
 
 #ifndef F8W_TM
 #define F8W_TM 64  // tokens per tile (docs/PERFORMANCE.md, "FP8 prefill")
@@ -43,27 +35,6 @@
 #define F8W_MZ (F8W_TM / 16)
 #define F8W_SLAB (16 * F8W_TM)  // 16-byte slots per buffer
 static_assert(F8W_TM >= 64 && F8W_TM % 16 == 0, "tile is whole 16-token MFMAs");
-
-__device__ __forceinline__ int f8w_swz(int c) {
-  return ((c & 3) << 1) | ((c >> 2) & 1);
-}
-
-// Gather side: thread tid owns chunk c = tid & 15 of rows j * 16 + tid / 16.
-struct F8WStage {
-  f16x8 v[F8W_MZ];
-  __device__ __forceinline__ void load(const _Float16* (&rowp)[F8W_MZ],
-                                       int kb, int c) {
-#pragma unroll
-    for (int j = 0; j < F8W_MZ; ++j)
-      v[j] = *reinterpret_cast<const f16x8*>(rowp[j] + kb * F8_KB + c * 8);
-  }
-  __device__ __forceinline__ void store(f16x8* buf, int r, int c) const {
-    const int sw = f8w_swz(c);
-#pragma unroll
-    for (int j = 0; j < F8W_MZ; ++j)
-      buf[c * F8W_TM + ((j * 16 + r) ^ sw)] = v[j];
-  }
-};
 
 // The k loop of one tile: NW weight matrices (gate and up, or down alone)
 // against the shared slab.  acc[w][z] is the 16 x 16 tile of matrix w and
@@ -80,7 +51,7 @@ __device__ __forceinline__ void f8w_tile(
   const int q = lane >> 4, tok = lane & 15;
   const int sr = threadIdx.x >> 4, scn = threadIdx.x & 15;
 
-  F8WStage st;
+  WideStage<F8W_TM> st;
   F8Lane wl[NW];
   st.load(rowp, 0, scn);
 #pragma unroll
@@ -110,7 +81,7 @@ __device__ __forceinline__ void f8w_tile(
       for (int w = 0; w < NW; ++w) wf[w] = wl[w].frag(i);
       const int c = q * 4 + i;
       const f16x8* col = cur + c * F8W_TM;
-      const int sw = f8w_swz(c);
+      const int sw = ws_swz(c);
 #pragma unroll
       for (int z = 0; z < F8W_MZ; ++z) {
         if (z < nz) {  // wave-uniform

@@ -463,6 +463,121 @@ def bench_fp8_prefill(ops, ext, dev="cuda", windows=3, iters=3):
         os.environ.pop(k, None)
 
 
+def bench_w4_prefill(ops, ext, dev="cuda", windows=3, iters=3):
+    """One DeepSeek-V2-Lite MoE layer (E=64, H=2048, I=1408, top-6) and one
+    DeepSeek-V3 layer (E=256, H=7168, I=2048, top-8), 4-bit gs 64 experts,
+    seeded random routing, prefilled at N=512 and N=4096 tokens: the packed
+    wide-tile route against the no-resident dense route
+    (MLXS_AMD_W4_PREFILL=dense with the dq-cache off: dequantize every
+    call), and for information the resident dense route (dq-cache on).
+    Same process, alternating, `windows` timed windows of `iters` calls
+    each after one warm-up call; prints median and min-max ms and the
+    peak-memory growth of one call per route, then each wide kernel alone
+    with its achieved packed-weight bytes/s (every activated expert's words
+    counted once) and FLOP/s, both computed from shapes."""
+    import os
+    gs, bits = 64, 4
+    TM = ext.moe_w4f16_wide_tile()
+    g = torch.Generator(device=dev).manual_seed(3)
+    keys = ("MLXS_AMD_W4_PREFILL", "MLXS_AMD_NO_DQ_CACHE")
+    env = {"packed": {"MLXS_AMD_W4_PREFILL": "packed"},
+           "dense": {"MLXS_AMD_W4_PREFILL": "dense",
+                     "MLXS_AMD_NO_DQ_CACHE": "1"},
+           "resident": {}}
+
+    def trip(O, Kd):
+        wq = torch.randint(-2 ** 31, 2 ** 31 - 1, (E, O, Kd * bits // 32),
+                           device=dev, dtype=torch.int32, generator=g)
+        sc = (torch.rand(E, O, Kd // gs, device=dev, generator=g) * 4e-3
+              + 4e-3).to(torch.bfloat16)
+        return wq, sc, (-7.5 * sc.float()).to(torch.bfloat16)
+
+    for name, E, H, I, K in (("V2-Lite", 64, 2048, 1408, 6),
+                             ("V3", 256, 7168, 2048, 8)):
+        gate, up, down = trip(I, H), trip(I, H), trip(H, I)
+
+        def run(route, x, w, idx):
+            for k in keys:
+                os.environ.pop(k, None)
+            os.environ.update(env[route])
+            # a fresh tensor object: the packed route pays its fp16 cast
+            return ops.grouped_expert_mlp_quant(x.view_as(x), gate, up, down,
+                                                w, idx, gs, bits)
+
+        print(f"w4 prefill, one {name} MoE layer: E={E} H={H} I={I} top-{K}, "
+              f"{bits}-bit gs {gs}, wide tile TM={TM}")
+        for N in (512, 4096):
+            x = (torch.randn(N, H, device=dev, generator=g) * 0.1) \
+                .to(torch.bfloat16)
+            idx = torch.rand(N, E, device=dev, generator=g) \
+                .topk(K, dim=-1).indices
+            w = torch.rand(N, K, device=dev, generator=g).to(torch.bfloat16)
+            ts, mem, outs = {"packed": [], "dense": []}, {}, {}
+            for route in ts:  # warm-up, and the memory of one call
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                outs[route] = run(route, x, w, idx).float()
+                torch.cuda.synchronize()
+                mem[route] = torch.cuda.max_memory_allocated() - base
+            diff = float((outs["packed"] - outs["dense"]).abs().max())
+            scale = float(outs["dense"].abs().max())
+            for _ in range(windows):  # alternate the two routes
+                for route in ts:
+                    ts[route].append(timeit(lambda: run(route, x, w, idx),
+                                            iters, warmup=0) / 1000)
+            print(f"  N={N}: max |packed - dense| {diff:.3e} at scale "
+                  f"{scale:.3e}")
+            for route, v in ts.items():
+                v.sort()
+                print(f"  N={N:5d} {route:8s} median {v[len(v) // 2]:8.2f} ms"
+                      f"  min {v[0]:8.2f}  max {v[-1]:8.2f}  "
+                      f"peak memory +{mem[route] / 2 ** 30:6.2f} GiB")
+            # the two wide kernels alone
+            s_e, s_off, s_cnt, s_tok, s_wt = ops.make_expert_subranges(
+                idx, w, E, max_tok=TM)[:5]
+            P = N * K
+            active = int((torch.bincount(idx.reshape(-1), minlength=E) > 0)
+                         .sum())
+            x16 = x.to(torch.float16)
+            gq, uq, dq = (ops.repack_w4(t[0], bits) for t in (gate, up, down))
+            gu = lambda: ext.moe_w4f16_gateup_wide(  # noqa: E731
+                x16, gq, uq, gate[1], gate[2], up[1], up[2], s_e, s_off,
+                s_cnt, s_tok, P, gs, bits)
+            hh = gu()
+            dn = lambda: ext.moe_w4f16_down_wide(  # noqa: E731
+                hh, dq, down[1], down[2], s_e, s_off, s_cnt, s_tok, s_wt, N,
+                gs, bits)
+            print(f"  N={N}: {active} experts active, "
+                  f"{int((s_cnt > 0).sum())} tiles of <= {TM} tokens")
+            for kn, fn, elems in (("gateup_wide", gu, 2 * I * H),
+                                  ("down_wide", dn, H * I)):
+                v = sorted(timeit(fn, iters, warmup=1) for _ in range(windows))
+                med = v[len(v) // 2]
+                print(f"  N={N:5d} {kn:12s} median {med / 1000:8.2f} ms  "
+                      f"min {v[0] / 1000:8.2f}  max {v[-1] / 1000:8.2f}  "
+                      f"{active * elems * bits / 8 / (med / 1e6) / 1e12:5.2f}"
+                      f" TB/s of weights  "
+                      f"{2.0 * P * elems / (med / 1e6) / 1e12:6.1f} TFLOP/s")
+            del x16, hh, outs
+        # for information: the resident dense route (builds its copy once)
+        for N in (512, 4096):
+            x = (torch.randn(N, H, device=dev, generator=g) * 0.1) \
+                .to(torch.bfloat16)
+            idx = torch.rand(N, E, device=dev, generator=g) \
+                .topk(K, dim=-1).indices
+            w = torch.rand(N, K, device=dev, generator=g).to(torch.bfloat16)
+            run("resident", x, w, idx)
+            v = sorted(timeit(lambda: run("resident", x, w, idx), iters,
+                              warmup=0) / 1000 for _ in range(windows))
+            print(f"  N={N:5d} resident median {v[len(v) // 2]:8.2f} ms  "
+                  f"min {v[0]:8.2f}  max {v[-1]:8.2f}")
+        del gate, up, down
+        torch.cuda.empty_cache()
+    for k in keys:
+        os.environ.pop(k, None)
+
+
 def bench_sample(ops, dev="cuda", windows=3, iters=20):
     """Batched sampling at DeepSeek-V3's vocabulary (V = 129 280), B in
     {1, 16, 64}, temperature 0.8, top_p in {1.0, 0.9}: one sample_rows
@@ -521,6 +636,9 @@ def main():
     ap.add_argument("--fp8-prefill", action="store_true",
                     help="only the FP8 MoE prefill comparison: packed "
                          "wide-tile route vs dequant per call")
+    ap.add_argument("--w4-prefill", action="store_true",
+                    help="only the w4 MoE prefill comparison: packed "
+                         "wide-tile route vs dequant per call")
     ap.add_argument("--fp8-only", action="store_true",
                     help="only the FP8-block vs 8-bit-affine comparison")
     ap.add_argument("--gate-only", action="store_true",
@@ -569,6 +687,9 @@ def main():
         return
     if args.fp8_prefill:
         bench_fp8_prefill(ops, ext, dev)
+        return
+    if args.w4_prefill:
+        bench_w4_prefill(ops, ext, dev)
         return
 
     E, H, I, N, K = 64, 2048, 1408, 64, 6
