@@ -255,8 +255,10 @@ def _prefill_attention_gpu(q, k, v, scale, causal_offset, softcap, sliding_windo
     B, Hq, Tq, Dk = q.shape
     Hkv, S = k.shape[1], k.shape[2]
     G = Hq // Hkv
-    qg = q.view(B, Hkv, G, Tq, Dk)
-    scores = torch.matmul(qg, k.unsqueeze(2).transpose(-1, -2)).float() * scale
+    # fp32 QK^T: a bf16 GEMM output rounds each score to 8 bits, which at
+    # |score| ~ 16 moves a key's weight by 3% (4x the bf16 output rounding)
+    qg = q.view(B, Hkv, G, Tq, Dk).float()
+    scores = torch.matmul(qg, k.unsqueeze(2).transpose(-1, -2).float()) * scale
     if softcap and softcap > 0:
         scores = torch.tanh(scores / softcap) * softcap
     qpos = torch.arange(Tq, device=q.device)[:, None] + causal_offset
