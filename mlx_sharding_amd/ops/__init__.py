@@ -135,6 +135,12 @@ def attention(q, k, v, scale: float, causal_offset: int = 0,
         ext = _require_ext("attention")
         cache_layout = k.stride(3) == 1 and k.stride(2) == k.shape[3]
         if q.shape[2] == 1 and cache_layout:
+            if (v.stride(2) == v.shape[3]
+                    and gqa_decode_route(q.shape[1] // k.shape[1], q.shape[3],
+                                         v.shape[3], q.shape[0], k.shape[1],
+                                         k.shape[2], pos_dev is not None)):
+                return ext.gqa_decode(q, k, v, scale, softcap, sliding_window,
+                                      pos_dev)
             return ext.attn_decode(q, k, v, scale, softcap, sliding_window,
                                    pos_dev)
         if (cache_layout
@@ -157,6 +163,65 @@ def attention(q, k, v, scale: float, causal_offset: int = 0,
                              causal_offset=S - 1, softcap=softcap,
                              sliding_window=sliding_window)
     return ref.attention(q, k, v, scale, causal_offset, softcap, sliding_window)
+
+
+_GQA_MFMA_ENV = "MLXS_AMD_GQA_MFMA"
+
+
+def gqa_decode_route(G: int, Dk: int, Dv: int, batch: int, hkv: int,
+                     span: int, device_pos: bool) -> bool:
+    """True when T == 1 attention of G = Hq/Hkv heads per KV head over
+    separate (Dk, Dv) caches should take the MFMA kernel (gqa_decode.hip).
+    ``span`` is the key extent of the cache view: the row length with a
+    host-side length, the whole capacity buffer under a device position
+    (``device_pos``).  MLXS_AMD_GQA_MFMA=0 never routes; =1 routes every
+    shape the kernel has an instantiation for at G >= 2.  Unset, only the
+    regions where the kernel beat attn_decode in every measured row by
+    more than the run-to-run spread are routed (PERFORMANCE.md, "GQA MFMA
+    flash-decode").  G = 1 reads each K/V byte for one head, where a
+    16-column MFMA tile is 15/16 padding: it is never routed by default."""
+    env = os.environ.get(_GQA_MFMA_ENV)
+    if env not in (None, "0", "1"):
+        raise ValueError(f"{_GQA_MFMA_ENV} must be 0 or 1, got {env!r}")
+    ext = hip_ext()
+    if (env == "0" or G < 2 or ext is None
+            or not ext.gqa_decode_shape_ok(G, Dk, Dv)):
+        return False
+    if env == "1":
+        return True
+    return _gqa_decode_measured(G, Dk, batch, hkv, span, device_pos)
+
+
+def _gqa_decode_measured(G: int, D: int, batch: int, hkv: int, span: int,
+                         device_pos: bool) -> bool:
+    """The default regions of gqa_decode_route: head dim 128 at G = 4, 7
+    and 8 (llama-3-8b, qwen2-7b, llama-3-70b) and head dim 64 at G = 8
+    (tinyllama), at every batch from 1 to 64 the table holds, with a
+    host-side length >= 512 or under a device position over a capacity
+    >= 2048 (there it won at every length from 512 keys to the capacity);
+    the kernel won each of those rows by 1.35x or more against a spread of
+    up to 11%.  At head dim 256 (gemma-2-9b, G = 2) it tied at batch 1, lost
+    one batch-16 row and won others by less than the spread, so that shape
+    stays on attn_decode, as does everything not measured."""
+    if device_pos and span < 2048 or span < 512:
+        return False
+    return (D == 128 and G in (4, 7, 8)) or (D == 64 and G == 8)
+
+
+def gqa_decode(q, k, v, scale: float, softcap: float = 0.0, window: int = 0,
+               pos=None):
+    """Grouped-query decode attention (T == 1) on the MFMA kernel.
+
+    q [B, Hq, 1, Dk] with any batch/head strides; k/v are cache views
+    [B, Hkv, S, D] over separate capacity buffers, 1 <= Hq/Hkv <= 16.
+    ``pos`` (int32 [1] or [B] on device) makes k/v the full capacity
+    buffers with row b attending over its first pos[b]+1 keys.  Returns
+    [B, Hq, 1, Dv]."""
+    if _use_hip(q):
+        return _require_ext("gqa_decode").gqa_decode(q, k, v, scale, softcap,
+                                                     window, pos)
+    return attention(q, k, v, scale, causal_offset=k.shape[2] - 1,
+                     softcap=softcap, sliding_window=window, pos_dev=pos)
 
 
 def mla_decode_enabled() -> bool:

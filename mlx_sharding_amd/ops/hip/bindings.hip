@@ -41,6 +41,10 @@ bool attn_decode_supported_shape(int, int);
 void launch_mla_decode(const void*, const void*, const void*, void*, float*,
                        float*, int, const int*, int, int, int, int, long, int,
                        int, float, long, long, long, long, hipStream_t);
+void launch_gqa_decode(const void*, const void*, const void*, void*, float*,
+                       float*, int, const int*, int, int, int, int, int, long,
+                       int, float, float, int, long, long, hipStream_t);
+bool gqa_decode_supported_shape(int, int, int);
 bool mla_decode_supported_shape(int, int, int);
 int mla_decode_nsplit(int, int, long);
 void launch_mla_chunk(const void*, const void*, const void*, void*, float*,
@@ -475,6 +479,18 @@ void mla_append_kv(torch::Tensor kvh, torch::Tensor kpe, torch::Tensor kcache,
                        cur_stream());
 }
 
+// Split-S factor of attn_decode and gqa_decode over a key span (the host
+// length, or the capacity under a device position): target ~1024 blocks,
+// slices of >= 512 keys (>= 256 keys when B*Hkv alone leaves the chip
+// block-starved, e.g. absorbed MLA with Hkv = 1).  The kernels derive the
+// slice length from it: ceil(span / nsplit) rounded up to 256 keys.
+int attn_decode_nsplit(int B, int Hkv, long span) {
+  const long slice = (B * Hkv <= 64) ? 256 : 512;
+  return (int)std::min<long>(
+      std::min<long>(8, std::max<long>(1, 1024 / std::max(1, B * Hkv))),
+      std::max<long>(1, (span + slice - 1) / slice));
+}
+
 // Shared body of attn_decode / attn_decode_split.
 // qn: [B, Hq, Dk - Dr] view (any batch/head strides, unit last stride);
 // qr: [B, Hq, Dr] view or undefined (Dr = 0).  head_major lays the
@@ -510,14 +526,7 @@ torch::Tensor attn_decode_impl(const torch::Tensor& qn, const torch::Tensor& qr,
   const long o_hs = head_major ? (long)B * Dv : Dv;
   int sbs;
   const int* s_ptr = pos_arg(pos, B, sbs);
-  // split-S for parallelism: target ~1024 blocks, slices of >= 512 keys
-  // (>= 256 keys when B*Hkv alone leaves the chip block-starved, e.g.
-  // absorbed MLA with Hkv = 1)
-  long span = s_ptr ? kScap : (long)S;
-  long slice = (B * Hkv <= 64) ? 256 : 512;
-  int nsplit = (int)std::min<long>(
-      std::min<long>(8, std::max<long>(1, 1024 / std::max(1, B * Hkv))),
-      std::max<long>(1, (span + slice - 1) / slice));
+  const int nsplit = attn_decode_nsplit(B, Hkv, s_ptr ? kScap : (long)S);
   float* part_o = nullptr;
   float* part_ml = nullptr;
   torch::Tensor po, pml;
@@ -567,6 +576,71 @@ torch::Tensor attn_decode_split(torch::Tensor q_nope, torch::Tensor q_rope,
               "q rows must be contiguous");
   return attn_decode_impl(q_nope, q_rope, k, v, scale, softcap, window, pos,
                           true);
+}
+
+// MFMA flash-decode for grouped-query attention (gqa_decode.hip).
+// q [B, Hq, 1, Dk] is read in place through its (batch, head) strides; k/v
+// are cache views [B, Hkv, S, D] over separate [B, Hkv, Scap, D] buffers.
+// Returns [B, Hq, 1, Dv].
+torch::Tensor gqa_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                         double scale, double softcap, int64_t window,
+                         c10::optional<torch::Tensor> pos) {
+  check_bf16(q, "q");
+  check_bf16(k, "k");
+  check_bf16(v, "v");
+  TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "gqa_decode needs Tq == 1");
+  TORCH_CHECK(k.dim() == 4 && v.dim() == 4, "k/v must be [B, Hkv, S, D]");
+  const int B = q.size(0), Hq = q.size(1), Dk = q.size(3);
+  const int Hkv = k.size(1), S = k.size(2), Dv = v.size(3);
+  TORCH_CHECK(k.size(3) == Dk, "q/K row width mismatch");
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && v.size(1) == Hkv &&
+                  v.size(2) == S, "k/v must match q's batch and each other");
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "Hq must be divisible by Hkv");
+  const int G = Hq / Hkv;
+  TORCH_CHECK(G >= 1 && G <= 16, "gqa_decode serves 1 to 16 heads per KV "
+              "head, got ", G);
+  TORCH_CHECK(v.stride(2) == Dv,
+              "V rows must be their own cache (v.stride(2) == Dv), not "
+              "aliased into the K rows");
+  TORCH_CHECK(gqa_decode_supported_shape(G, Dk, Dv),
+              "gqa_decode: unsupported shape G=", G, " Dk=", Dk, " Dv=", Dv);
+  TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1,
+              "q/K/V rows must be contiguous");
+  TORCH_CHECK(k.stride(2) == Dk, "K seq stride mismatch");
+  TORCH_CHECK(k.stride(1) % Dk == 0 && v.stride(1) % Dv == 0,
+              "K/V head stride must be a whole number of rows");
+  const long kScap = k.stride(1) / Dk;
+  const long vScap = v.stride(1) / Dv;
+  TORCH_CHECK(kScap == vScap, "K/V capacity mismatch");
+  TORCH_CHECK(kScap >= S, "K/V view longer than its capacity");
+  TORCH_CHECK(B == 1 || (k.stride(0) == Hkv * k.stride(1) &&
+                         v.stride(0) == Hkv * v.stride(1)),
+              "K/V batch stride must be Hkv whole heads");
+  // the kernel reads q, K and V with 16-byte loads
+  auto al16 = [](const torch::Tensor& t) {
+    return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
+  };
+  TORCH_CHECK(al16(q) && al16(k) && al16(v) && q.stride(0) % 8 == 0 &&
+                  q.stride(1) % 8 == 0, "q/K/V rows must be 16-byte aligned");
+  int sbs;
+  const int* s_ptr = pos_arg(pos, B, sbs);
+  const int nsplit = attn_decode_nsplit(B, Hkv, s_ptr ? kScap : (long)S);
+  auto out = torch::empty({B, Hq, 1, Dv}, q.options());
+  float* part_o = nullptr;
+  float* part_ml = nullptr;
+  torch::Tensor po, pml;
+  if (nsplit > 1) {
+    auto fopts = q.options().dtype(torch::kFloat32);
+    po = torch::empty({(long)B * Hq * nsplit * Dv}, fopts);
+    pml = torch::empty({(long)B * Hq * nsplit * 2}, fopts);
+    part_o = po.data_ptr<float>();
+    part_ml = pml.data_ptr<float>();
+  }
+  launch_gqa_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                    part_o, part_ml, nsplit, s_ptr, sbs, B, Hq, Hkv, S, kScap,
+                    Dk, (float)scale, (float)softcap, (int)window,
+                    q.stride(0), q.stride(1), cur_stream());
+  return out;
 }
 
 // MFMA flash-decode for absorbed MLA (mla_decode.hip).  q_nope
@@ -1663,6 +1737,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("window"), pybind11::arg("pos") = pybind11::none());
   m.def("attn_decode_shape_ok", [](int64_t g, int64_t dv) {
     return attn_decode_supported_shape((int)g, (int)dv);
+  });
+  m.def("gqa_decode", &gqa_decode, pybind11::arg("q"), pybind11::arg("k"),
+        pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("softcap"),
+        pybind11::arg("window"), pybind11::arg("pos") = pybind11::none());
+  m.def("gqa_decode_shape_ok", [](int64_t g, int64_t dk, int64_t dv) {
+    return gqa_decode_supported_shape((int)g, (int)dk, (int)dv);
   });
   m.def("mla_decode", &mla_decode, pybind11::arg("q_nope"),
         pybind11::arg("q_rope"), pybind11::arg("kv"), pybind11::arg("rank"),

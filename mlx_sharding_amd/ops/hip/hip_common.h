@@ -18,6 +18,15 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
+// The MFMA flash-decode kernels (mla_decode.hip, gqa_decode.hip) are built
+// without the packed-fp32 VALU forms (v_pk_mul_f32 and kin): their
+// accumulator rescale must not be fused into them.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MD_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define MD_NO_PK_F32
+#endif
+
 // v_dot2c_f32_bf16: 2 bf16 products + f32 accumulate in ONE VALU instr
 // (gfx950) — same numerics as cvt+fma chains with f32 accumulation.
 __device__ __forceinline__ float dot2_bf16(bf16x2_t a, bf16x2_t b, float c) {

@@ -113,14 +113,6 @@
 
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 
-// The kernel is built without the packed-fp32 VALU forms (v_pk_mul_f32
-// and kin): its accumulator rescale must not be fused into them.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MD_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define MD_NO_PK_F32
-#endif
-
 // Tile staging, shared by both kernels.  The macros expect in scope: tid,
 // NT, NIT, NITEMS, DK, DV, KSTR, kvb, hi, k_lds, vt_lds; STG is the prefetch
 // register set, a `short8v [NIT][4]`.  item = tid + it*NT -> chunk

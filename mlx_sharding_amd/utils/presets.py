@@ -257,6 +257,33 @@ PRESETS["debug-deepseek-v3-fp8"] = dict(
     moe_intermediate_size=128,
 )
 
+# debug-llama with 8 heads of 64 over 2 KV heads: G = 4, the MFMA GQA decode
+# kernel (gqa_decode_kernel)
+PRESETS["debug-llama-gqa"] = dict(
+    PRESETS["debug-llama"],
+    hidden_size=512,
+    num_key_value_heads=2,
+)
+
+# a small gemma2 for the same kernel: G = 2 at head dim 64 with the attention
+# softcap and a sliding window a short decode already exceeds
+PRESETS["debug-gemma2"] = {
+    "model_type": "gemma2",
+    "hidden_size": 256,
+    "num_hidden_layers": 4,
+    "intermediate_size": 128,
+    "num_attention_heads": 4,
+    "num_key_value_heads": 2,
+    "head_dim": 64,
+    "vocab_size": 128,
+    "rms_norm_eps": 1e-6,
+    "rope_theta": 10000.0,
+    "query_pre_attn_scalar": 16,
+    "attn_logit_softcapping": 50.0,
+    "final_logit_softcapping": 30.0,
+    "sliding_window": 8,
+}
+
 
 def get_preset(name: str, quant: bool = False,
                group_size: int = 64, bits: int = 4,

@@ -211,6 +211,60 @@ def bench_mla(ops, ext, dev="cuda", iters=200):
                       f"-> {100 * bound / med:5.1f}%", flush=True)
 
 
+def _window_us(fn, window_s):
+    """us per call over one timed window of about window_s seconds."""
+    return timeit(fn, max(10, int(window_s * 1e6 / timeit(fn, 10, 5))), 0)
+
+
+def bench_gqa_decode(ext, dev="cuda", window_s=0.25, batches=(1, 16, 64),
+                     lengths=(512, 2048, 4096, 8192)):
+    """GQA decode attention: the scalar attn_decode kernel and the MFMA
+    gqa_decode kernel, alternated in one process on the same tensors after
+    warm-up, two rounds of one window each.  Shapes (Hq, Hkv, D): llama-3-70b
+    (64, 8, 128), llama-3-8b (32, 8, 128), qwen2-7b (28, 4, 128), tinyllama
+    (32, 4, 64), gemma-2-9b (16, 8, 256) with softcap 50 / window 4096 and
+    without a window.  "host" passes a view of L keys; "device" an int32 [B]
+    position L - 1 over the whole capacity (the largest length).  TB/s is
+    B*Hkv*L*(Dk+Dv)*2 bytes (of the keys inside the window) over the faster
+    round."""
+    shapes = [(64, 8, 128, 0.0, 0), (32, 8, 128, 0.0, 0), (28, 4, 128, 0.0, 0),
+              (32, 4, 64, 0.0, 0), (16, 8, 256, 50.0, 4096),
+              (16, 8, 256, 50.0, 0)]
+    cap, bmax = max(lengths), max(batches)
+    print("Hq Hkv D cap window B L mode: attn_decode us (r0 r1) TB/s | "
+          "gqa_decode us (r0 r1) TB/s | old/new (min..max over rounds)")
+    for Hq, Hkv, D, softcap, window in shapes:
+        scale = D ** -0.5
+        qb = torch.randn(bmax, Hq, 1, D, dtype=torch.bfloat16, device=dev)
+        kb = torch.randn(bmax, Hkv, cap, D, dtype=torch.bfloat16, device=dev)
+        vb = torch.randn(bmax, Hkv, cap, D, dtype=torch.bfloat16, device=dev)
+        for B in batches:
+            for L in lengths:
+                for mode in ("host", "device"):
+                    q = qb[:B]
+                    if mode == "host":
+                        k, v, pos = kb[:B, :, :L], vb[:B, :, :L], None
+                    else:
+                        k, v = kb[:B], vb[:B]
+                        pos = torch.full((B,), L - 1, dtype=torch.int32,
+                                         device=dev)
+                    a = (q, k, v, scale, softcap, window, pos)
+                    fns = (lambda: ext.attn_decode(*a),
+                           lambda: ext.gqa_decode(*a))
+                    diff = (fns[0]().float() - fns[1]().float()).abs().max()
+                    t = [[_window_us(fn, window_s) for fn in fns]
+                         for _ in range(2)]  # alternate the two kernels
+                    old, new = (t[0][0], t[1][0]), (t[0][1], t[1][1])
+                    live = min(L, window) if window else L
+                    tb = B * Hkv * live * 2 * D * 2 / 1e6
+                    print(f"{Hq:2d} {Hkv} {D:3d} cap{softcap:g} w{window:<4d} "
+                          f"B={B:2d} L={L:4d} {mode:6s}: "
+                          f"{old[0]:7.1f} {old[1]:7.1f} {tb / min(old):5.2f} | "
+                          f"{new[0]:7.1f} {new[1]:7.1f} {tb / min(new):5.2f} | "
+                          f"{min(old) / max(new):5.2f}..{max(old) / min(new):5.2f}"
+                          f"  diff {diff.item():.1e}", flush=True)
+
+
 def bench_mla_chunk(ops, ext, dev="cuda", iters=200):
     """One layer's attention section for T new tokens over a cached prefix
     of a V2-Lite / V3 geometry (rows 576 / 512, nope 128, vd 128), B=1, two
@@ -653,6 +707,13 @@ def main():
     ap.add_argument("--mla-chunk", action="store_true",
                     help="only the short-chunk-over-a-prefix comparison: "
                          "expanded prefill vs the absorbed mla_chunk path")
+    ap.add_argument("--gqa-decode", action="store_true",
+                    help="only the GQA decode comparison: the scalar "
+                         "attn_decode kernel vs the MFMA gqa_decode kernel")
+    ap.add_argument("--lengths", type=int, nargs="+",
+                    default=[512, 2048, 4096, 8192],
+                    help="key lengths of --gqa-decode; the largest is the "
+                         "capacity of the device-position rows")
     ap.add_argument("--moe-route", action="store_true",
                     help="only the prefill routing comparison: the fused "
                          "moe_route kernels vs the torch gate + sort")
@@ -666,6 +727,9 @@ def main():
 
     if args.moe_route:
         bench_moe_route(ops, ref, dev)
+        return
+    if args.gqa_decode:
+        bench_gqa_decode(ext, dev, lengths=tuple(args.lengths))
         return
     if args.mla_only:
         bench_mla(ops, ext, dev)
