@@ -29,9 +29,15 @@ def main(argv=None):
                    help="continuous batching: decode up to N concurrent "
                         "requests in one batched step (default "
                         "MLXS_MAX_BATCH or 1 = off; world size 1 only)")
+    p.add_argument("--kv-dtype", choices=["bf16", "fp8"], default=None,
+                   help="KV cache dtype (sets MLXS_AMD_KV_DTYPE): fp8 halves "
+                        "the cache of llama-family models, head dim 64/128")
     args = p.parse_args(argv)
     if not 1 <= args.max_batch <= MAX_BATCH_LIMIT:
         p.error(f"--max-batch must be in [1, {MAX_BATCH_LIMIT}]")
+    if args.kv_dtype:
+        import os
+        os.environ["MLXS_AMD_KV_DTYPE"] = args.kv_dtype
 
     from transformers import AutoTokenizer
 

@@ -11,6 +11,7 @@ consistent without num_hidden_layers dummy entries.
 
 from __future__ import annotations
 
+import os
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -21,6 +22,8 @@ from ..config import ModelConfig, QuantConfig, ShardSpec
 from ..ops.kvcache import KVCache
 
 QuantPredicate = Callable[[str], bool]
+
+KV_DTYPE_ENV = "MLXS_AMD_KV_DTYPE"  # bf16 (default) | fp8
 
 
 def fp8_block_params(shape, block: int = 128):
@@ -178,8 +181,36 @@ class StageModel(nn.Module):
         """(n_kv_heads, k_head_dim, v_head_dim) for each *owned* layer."""
         raise NotImplementedError
 
+    # llama-shaped attention (separate per-head K and V caches, half-split
+    # rope, no softcap or window): the families the FP8 KV cache serves
+    kv_fp8_family = False
+
+    def _kv_dtype(self, dtype: Optional[torch.dtype]) -> Optional[torch.dtype]:
+        """The cache dtype: the argument, else MLXS_AMD_KV_DTYPE (unset or
+        ``bf16``: the activation dtype, as ever; ``fp8``: the FP8 cache).
+        An FP8 cache needs a llama-family stage with head dim 64 or 128."""
+        if dtype is None:
+            env = os.environ.get(KV_DTYPE_ENV)
+            if env not in (None, "", "bf16", "fp8"):
+                raise ValueError(
+                    f"{KV_DTYPE_ENV} must be bf16 or fp8, got {env!r}")
+            if env == "fp8":
+                dtype = torch.float8_e4m3fn
+        if dtype == torch.float8_e4m3fn:
+            specs = self.cache_specs()
+            if not self.kv_fp8_family or any(
+                    kd != vd or kd not in (64, 128) for _, kd, vd in specs):
+                raise ValueError(
+                    "the FP8 KV cache serves llama-family models (llama, "
+                    "mistral, qwen2, tinyllama) with per-layer caches "
+                    "(Hkv, D, D), D in {64, 128}; "
+                    f"{self.config.model_type} has "
+                    f"{sorted(set((kd, vd) for _, kd, vd in specs))}")
+        return dtype
+
     def make_cache(self, dtype: Optional[torch.dtype] = None, batch_size: int = 1,
                    device=None) -> List[KVCache]:
+        dtype = self._kv_dtype(dtype)
         # dtype from the first FLOATING parameter: on a quantized stage
         # without embeddings the first parameter is a packed uint32
         # weight, and a uint32 KV cache silently truncates every K/V

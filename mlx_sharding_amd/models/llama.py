@@ -52,6 +52,8 @@ class LlamaAttention(nn.Module):
         q = ops.apply_rope(q, cos, sin).transpose(1, 2)
         offset = 0
         gp = None
+        if cache is not None and cache.fp8 and ops.use_native(x):
+            return self._attend_fp8(q, k, v, cos, sin, cache)
         if cache is not None and ops.use_native(x):
             # fused rope-k + scatter into the caches (one kernel instead
             # of rope + two index_copy launches)
@@ -71,6 +73,28 @@ class LlamaAttention(nn.Module):
                             pos_dev=gp)
         out = out.transpose(1, 2).reshape(B, T, -1)
         return self.o_proj(out)
+
+    def _attend_fp8(self, q, k, v, cos, sin, cache: KVCache) -> torch.Tensor:
+        """Attention over an FP8 KV cache on the GPU.  The new rows are roped,
+        quantized and appended by one kernel; T == 1 runs the FP8 flash-decode
+        kernel on the bytes, T > 1 (cold or chunked prefill, prefix-cache
+        tails) dequantizes the cached rows into bf16 scratch for the existing
+        prefill attention.  Prefill and decode therefore attend the SAME
+        quantized values, new rows included, so cold-vs-chunked prefill and
+        prefix-cache reuse stay equal to one another as with a bf16 cache."""
+        B, _, T, _ = q.shape
+        gp = cache.graph_pos
+        offset = 0 if gp is not None else cache.offset
+        k8, ks, v8, vs = cache.append_rope_kv_fp8(k, v, cos, sin)
+        if T == 1:
+            out = ops.gqa_decode_fp8(q, k8, ks, v8, vs, self.scale, pos=gp,
+                                     length=None if gp is not None
+                                     else cache.offset)
+        else:
+            kd, vd = cache.dequant_views()
+            out = ops.attention(q, kd, vd, self.scale, causal_offset=offset,
+                                pos_dev=gp)
+        return self.o_proj(out.transpose(1, 2).reshape(B, T, -1))
 
 
 class LlamaMLP(nn.Module):
@@ -116,6 +140,7 @@ class _Inner(nn.Module):
 
 class LlamaStageModel(StageModel):
     model_type = "llama"
+    kv_fp8_family = True
 
     def __init__(self, config: ModelConfig, shard: ShardSpec, quant_for=None):
         super().__init__(config, shard)

@@ -224,6 +224,56 @@ def gqa_decode(q, k, v, scale: float, softcap: float = 0.0, window: int = 0,
                      softcap=softcap, sliding_window=window, pos_dev=pos)
 
 
+def kv_fp8_quantize(x):
+    """FP8 KV-cache quantization of rows x [..., D] (bf16): (bytes uint8
+    [..., D], power-of-two scale fp32 [...]); the format is specified by
+    reference.kv_fp8_quantize.  On the GPU (D 64 or 128) it runs the append
+    kernel's quantizer and is bit-identical to the reference."""
+    if _use_hip(x):
+        ext = _require_ext("kv_fp8_quantize")
+        D = x.shape[-1]
+        rows = x.reshape(-1, 1, 1, D)
+        codes = torch.empty(rows.shape, dtype=torch.uint8, device=x.device)
+        scale = torch.empty(rows.shape[:3], dtype=torch.float32,
+                            device=x.device)
+        ext.rope_append_kv_fp8(None, rows, None, None, None, None, codes,
+                               scale)
+        return codes.view(x.shape), scale.view(x.shape[:-1])
+    return ref.kv_fp8_quantize(x)
+
+
+def kv_fp8_dequantize(codes, scale):
+    """bytes [..., D] + scale [...] of the FP8 KV cache -> bf16 [..., D]."""
+    if _use_hip(codes):
+        ext = _require_ext("kv_fp8_dequantize")
+        D = codes.shape[-1]
+        c = codes.reshape(1, 1, -1, D)
+        out = ext.kv_fp8_dequant(c, scale.reshape(1, 1, -1).float(),
+                                 c.shape[2])
+        return out.view(codes.shape)
+    return ref.kv_fp8_dequantize(codes, scale)
+
+
+def gqa_decode_fp8(q, k8, ks, v8, vs, scale: float, pos=None, length=None):
+    """Grouped-query decode attention (T == 1) over an FP8 KV cache.
+
+    q [B, Hq, 1, D] bf16; k8 / v8 are the byte buffers [B, Hkv, Scap, D]
+    with their fp32 scales ks / vs [B, Hkv, Scap]; D is 64 or 128 and
+    1 <= Hq/Hkv <= 16.  Rows attend their first ``length`` keys (the whole
+    capacity when None), or, with ``pos`` (int32 [1] or [B] on device), row
+    b attends its first pos[b] + 1 keys.  An FP8 cache has only this kernel
+    on the GPU: there is no routing and no fallback.  Returns
+    [B, Hq, 1, D]."""
+    if _use_hip(q):
+        return _require_ext("gqa_decode_fp8").gqa_decode_fp8(
+            q, k8, ks, v8, vs, scale, pos,
+            -1 if length is None else int(length))
+    S = k8.shape[2] if (length is None or pos is not None) else int(length)
+    k = ref.kv_fp8_dequantize(k8[:, :, :S], ks[:, :, :S])
+    v = ref.kv_fp8_dequantize(v8[:, :, :S], vs[:, :, :S])
+    return attention(q, k, v, scale, causal_offset=S - 1, pos_dev=pos)
+
+
 def mla_decode_enabled() -> bool:
     """The MFMA absorbed-MLA decode kernel (mla_decode.hip) serves the
     shapes it supports.  MLXS_AMD_NO_MLA_MFMA=1 keeps them on the

@@ -45,6 +45,17 @@ void launch_gqa_decode(const void*, const void*, const void*, void*, float*,
                        float*, int, const int*, int, int, int, int, int, long,
                        int, float, float, int, long, long, hipStream_t);
 bool gqa_decode_supported_shape(int, int, int);
+void launch_rope_append_kv_fp8(const void*, const void*, const float*,
+                               const float*, void*, float*, void*, float*,
+                               const int*, int, int, int, int, int, int, long,
+                               long, long, long, hipStream_t);
+void launch_kv_fp8_dequant(const void*, const float*, void*, long, int, long,
+                           int, hipStream_t);
+void launch_gqa_decode_fp8(const void*, const void*, const float*,
+                           const void*, const float*, void*, float*, float*,
+                           int, const int*, int, int, int, int, int, long,
+                           int, float, long, long, hipStream_t);
+bool gqa_decode_fp8_supported_shape(int, int, int);
 bool mla_decode_supported_shape(int, int, int);
 int mla_decode_nsplit(int, int, long);
 void launch_mla_chunk(const void*, const void*, const void*, void*, float*,
@@ -640,6 +651,151 @@ torch::Tensor gqa_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                     part_o, part_ml, nsplit, s_ptr, sbs, B, Hq, Hkv, S, kScap,
                     Dk, (float)scale, (float)softcap, (int)window,
                     q.stride(0), q.stride(1), cur_stream());
+  return out;
+}
+
+// ---- FP8 KV cache (kv_fp8.hip) ----
+// A byte cache [B, Hkv, Scap, D] (uint8 or float8_e4m3fn, contiguous) with
+// its fp32 scales [B, Hkv, Scap] (contiguous).
+void check_kv8_buffer(const torch::Tensor& c, const torch::Tensor& s,
+                      const char* name) {
+  TORCH_CHECK(c.is_cuda() && s.is_cuda(), name, " cache must be on GPU");
+  TORCH_CHECK(c.scalar_type() == torch::kUInt8 ||
+                  c.scalar_type() == torch::kFloat8_e4m3fn,
+              name, " cache must be uint8 or float8_e4m3fn");
+  TORCH_CHECK(s.scalar_type() == torch::kFloat32, name,
+              " scales must be fp32");
+  TORCH_CHECK(c.dim() == 4 && c.is_contiguous(), name,
+              " cache must be a contiguous [B, Hkv, Scap, D] buffer");
+  TORCH_CHECK(s.dim() == 3 && s.is_contiguous() && s.size(0) == c.size(0) &&
+                  s.size(1) == c.size(1) && s.size(2) == c.size(2),
+              name, " scales must be contiguous with the cache's leading "
+              "shape [B, Hkv, Scap]");
+  TORCH_CHECK(c.size(3) == 64 || c.size(3) == 128, name,
+              " cache: unsupported shape D=", c.size(3));
+}
+
+// k/v [B, T, Hkv, D] bf16; byte caches + scales, full buffers.  An undefined
+// k quantizes the rows of v alone (no rope, no K cache).
+void rope_append_kv_fp8(c10::optional<torch::Tensor> k, torch::Tensor v,
+                        c10::optional<torch::Tensor> cos,
+                        c10::optional<torch::Tensor> sin,
+                        c10::optional<torch::Tensor> kcache,
+                        c10::optional<torch::Tensor> kscale,
+                        torch::Tensor vcache, torch::Tensor vscale,
+                        c10::optional<torch::Tensor> pos, int64_t pos0) {
+  check_bf16(v, "v");
+  TORCH_CHECK(v.dim() == 4, "v must be [B, T, Hkv, D]");
+  const int B = v.size(0), T = v.size(1), Hkv = v.size(2), D = v.size(3);
+  check_kv8_buffer(vcache, vscale, "V");
+  TORCH_CHECK(vcache.size(0) == B && vcache.size(1) == Hkv &&
+                  vcache.size(3) == D, "V cache shape mismatch");
+  const long Scap = vcache.size(2);
+  int pbs;
+  const int* pp = pos_arg(pos, B, pbs);
+  TORCH_CHECK(pp || (pos0 >= 0 && pos0 + T <= Scap),
+              "append past the cache capacity");
+  // fused-qkv split views read in place (heads contiguous within a slice,
+  // rows 8-byte aligned for the kernel's b64 loads)
+  auto view_ok = [&](const torch::Tensor& t) {
+    return t.stride(3) == 1 && t.stride(2) == D
+        && t.stride(0) == t.size(1) * t.stride(1) && t.stride(1) % 4 == 0
+        && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 7) == 0;
+  };
+  torch::Tensor kv, vv = v, cc, sc;
+  long krs = (long)Hkv * D, vrs = (long)Hkv * D, csb = 0;
+  if (view_ok(v)) vrs = v.stride(1); else vv = v.contiguous();
+  if (k.has_value()) {
+    check_bf16(*k, "k");
+    TORCH_CHECK(k->sizes() == v.sizes(), "k/v shape mismatch");
+    TORCH_CHECK(cos.has_value() && sin.has_value() && kcache.has_value() &&
+                    kscale.has_value(), "k needs cos, sin and a K cache");
+    check_kv8_buffer(*kcache, *kscale, "K");
+    TORCH_CHECK(kcache->sizes() == vcache.sizes(), "K/V cache shape mismatch");
+    cc = cos->contiguous();
+    sc = sin->contiguous();
+    csb = rope_table_bstride(cc, sc, B, T, D / 2);
+    kv = *k;
+    if (view_ok(kv)) krs = kv.stride(1); else kv = kv.contiguous();
+  }
+  const bool hk = k.has_value();
+  launch_rope_append_kv_fp8(
+      hk ? kv.data_ptr() : nullptr, vv.data_ptr(),
+      hk ? cc.data_ptr<float>() : nullptr, hk ? sc.data_ptr<float>() : nullptr,
+      hk ? kcache->data_ptr() : nullptr,
+      hk ? kscale->data_ptr<float>() : nullptr, vcache.data_ptr(),
+      vscale.data_ptr<float>(), pp, pbs, (int)pos0, B, T, Hkv, D, Scap, krs,
+      vrs, csb, cur_stream());
+}
+
+// rows [0, S) of a byte cache + scales -> contiguous bf16 [B, Hkv, S, D]
+torch::Tensor kv_fp8_dequant(torch::Tensor cache, torch::Tensor scales,
+                             int64_t S) {
+  check_kv8_buffer(cache, scales, "KV");
+  const long B = cache.size(0), Hkv = cache.size(1), Scap = cache.size(2);
+  const int D = cache.size(3);
+  TORCH_CHECK(S >= 0 && S <= Scap, "S outside the capacity");
+  auto out = torch::empty({B, Hkv, S, (long)D},
+                          cache.options().dtype(torch::kBFloat16));
+  launch_kv_fp8_dequant(cache.data_ptr(), scales.data_ptr<float>(),
+                        out.data_ptr(), B * Hkv, (int)S, Scap, D,
+                        cur_stream());
+  return out;
+}
+
+// MFMA flash-decode over the FP8 caches.  q [B, Hq, 1, D] bf16 is read in
+// place through its (batch, head) strides; k8 / v8 are the full byte
+// buffers with their scales.  With a host length (pos undefined) rows attend
+// their first S keys; with pos (int32 [1] or [B]) row b attends pos[b] + 1.
+// Returns [B, Hq, 1, D].
+torch::Tensor gqa_decode_fp8(torch::Tensor q, torch::Tensor k8,
+                             torch::Tensor ks, torch::Tensor v8,
+                             torch::Tensor vs, double scale,
+                             c10::optional<torch::Tensor> pos, int64_t S) {
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "gqa_decode_fp8 needs Tq == 1");
+  TORCH_CHECK(k8.dim() == 4 && v8.dim() == 4, "k8/v8 must be [B, Hkv, Scap, D]");
+  const int B = q.size(0), Hq = q.size(1), Dk = q.size(3);
+  const int Hkv = k8.size(1), Dv = v8.size(3);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "Hq must be divisible by Hkv");
+  const int G = Hq / Hkv;
+  TORCH_CHECK(G >= 1 && G <= 16, "gqa_decode_fp8 serves 1 to 16 heads per "
+              "KV head, got ", G);
+  TORCH_CHECK(k8.size(3) == Dk && gqa_decode_fp8_supported_shape(G, Dk, Dv),
+              "gqa_decode_fp8: unsupported shape G=", G, " Dk=", k8.size(3),
+              " Dv=", Dv, " (q rows of ", Dk, ")");
+  check_kv8_buffer(k8, ks, "K");
+  check_kv8_buffer(v8, vs, "V");
+  TORCH_CHECK(k8.sizes() == v8.sizes() && k8.size(0) == B,
+              "k8/v8 must match q's batch and each other");
+  const long Scap = k8.size(2);
+  TORCH_CHECK(q.stride(3) == 1 && q.stride(0) % 8 == 0 &&
+                  q.stride(1) % 8 == 0 &&
+                  (reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0,
+              "q rows must be contiguous and 16-byte aligned");
+  int sbs;
+  const int* s_ptr = pos_arg(pos, B, sbs);
+  if (!s_ptr) {
+    if (S < 0) S = Scap;
+    TORCH_CHECK(S >= 1 && S <= Scap, "length outside [1, capacity]");
+  }
+  const int nsplit = attn_decode_nsplit(B, Hkv, s_ptr ? Scap : (long)S);
+  auto out = torch::empty({B, Hq, 1, Dv}, q.options());
+  float* part_o = nullptr;
+  float* part_ml = nullptr;
+  torch::Tensor po, pml;
+  if (nsplit > 1) {
+    auto fopts = q.options().dtype(torch::kFloat32);
+    po = torch::empty({(long)B * Hq * nsplit * Dv}, fopts);
+    pml = torch::empty({(long)B * Hq * nsplit * 2}, fopts);
+    part_o = po.data_ptr<float>();
+    part_ml = pml.data_ptr<float>();
+  }
+  launch_gqa_decode_fp8(q.data_ptr(), k8.data_ptr(), ks.data_ptr<float>(),
+                        v8.data_ptr(), vs.data_ptr<float>(), out.data_ptr(),
+                        part_o, part_ml, nsplit, s_ptr, sbs, B, Hq, Hkv,
+                        (int)S, Scap, Dk, (float)scale, q.stride(0),
+                        q.stride(1), cur_stream());
   return out;
 }
 
@@ -1743,6 +1899,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("window"), pybind11::arg("pos") = pybind11::none());
   m.def("gqa_decode_shape_ok", [](int64_t g, int64_t dk, int64_t dv) {
     return gqa_decode_supported_shape((int)g, (int)dk, (int)dv);
+  });
+  m.def("rope_append_kv_fp8", &rope_append_kv_fp8, pybind11::arg("k"),
+        pybind11::arg("v"), pybind11::arg("cos"), pybind11::arg("sin"),
+        pybind11::arg("kcache"), pybind11::arg("kscale"),
+        pybind11::arg("vcache"), pybind11::arg("vscale"),
+        pybind11::arg("pos") = pybind11::none(), pybind11::arg("pos0") = 0);
+  m.def("kv_fp8_dequant", &kv_fp8_dequant, pybind11::arg("cache"),
+        pybind11::arg("scales"), pybind11::arg("S"));
+  m.def("gqa_decode_fp8", &gqa_decode_fp8, pybind11::arg("q"),
+        pybind11::arg("k8"), pybind11::arg("ks"), pybind11::arg("v8"),
+        pybind11::arg("vs"), pybind11::arg("scale"),
+        pybind11::arg("pos") = pybind11::none(),
+        pybind11::arg("length") = -1);
+  m.def("gqa_decode_fp8_shape_ok", [](int64_t g, int64_t dk, int64_t dv) {
+    return gqa_decode_fp8_supported_shape((int)g, (int)dk, (int)dv);
   });
   m.def("mla_decode", &mla_decode, pybind11::arg("q_nope"),
         pybind11::arg("q_rope"), pybind11::arg("kv"), pybind11::arg("rank"),

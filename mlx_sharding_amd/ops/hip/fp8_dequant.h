@@ -33,6 +33,21 @@ __device__ __forceinline__ f16x8 fp8x8_to_f16(unsigned int w0,
   return out;
 }
 
+// 8 fp8 bytes in memory order -> one bf16x8 MFMA fragment in natural k
+// order (the FP8 KV cache, kv_fp8.hip).  Also exact: 4 significant bits
+// into 8, and bf16 has the wider exponent range
+// (v_cvt_scalef32_pk_bf16_fp8, scale held at 1.0).
+__device__ __forceinline__ bf16x8_t fp8x8_to_bf16(unsigned int w0,
+                                                  unsigned int w1) {
+  bf16x8_t out;
+  bf16x2_t* op = reinterpret_cast<bf16x2_t*>(&out);
+  op[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false);
+  op[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true);
+  op[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false);
+  op[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true);
+  return out;
+}
+
 // one fp8 byte -> fp32 (exact)
 __device__ __forceinline__ float fp8_to_f32(unsigned char b) {
   return __builtin_amdgcn_cvt_f32_fp8((int)b, 0);

@@ -31,6 +31,12 @@ class KVCache:
         if not dtype.is_floating_point:
             raise TypeError(f"KV cache dtype must be floating, got {dtype}")
         self.dtype = dtype
+        # FP8 cache: _k / _v hold e4m3 bytes (uint8) and _ks / _vs one fp32
+        # power-of-two scale per (row, kv head, position); the format is
+        # ops.reference.kv_fp8_quantize
+        self.fp8 = dtype == torch.float8_e4m3fn
+        self._ks: Optional[torch.Tensor] = None
+        self._vs: Optional[torch.Tensor] = None
         self.device = torch.device(device)
         self.batch_size = batch_size
         self.offset = 0
@@ -55,6 +61,8 @@ class KVCache:
             raise ValueError(f"KV cache capacity {cap} is fixed; "
                              f"{needed} positions needed")
         new_cap = ((needed + self.CHUNK - 1) // self.CHUNK) * self.CHUNK
+        if self.fp8:
+            return self._fp8_grow(batch, new_cap)
         nk = torch.empty(batch, self.n_kv_heads, new_cap, self.k_head_dim,
                          dtype=self.dtype, device=self.device)
         nv = torch.empty(batch, self.n_kv_heads, new_cap, self.v_head_dim,
@@ -70,7 +78,13 @@ class KVCache:
         In graph mode (graph_pos set) the append is an index_copy_ at the
         device position and the FULL buffers are returned — the caller
         passes graph_pos to the attention op, which reads the length on
-        device (capture-safe: no python-int shapes)."""
+        device (capture-safe: no python-int shapes).
+
+        An FP8 cache quantizes k/v with the reference (this is its CPU and
+        fallback path) and returns DEQUANTIZED bf16 tensors, so attention
+        sees what a later step will read back."""
+        if self.fp8:
+            return self._fp8_update(k, v)
         if self.graph_pos is not None:
             idx = self.graph_pos.to(torch.long)
             if idx.numel() > 1:  # per-row positions: row b lands at pos[b]
@@ -147,6 +161,85 @@ class KVCache:
         self.offset += T
         return (self._k[:, :, : self.offset], self._v[:, :, : self.offset])
 
+    # -- FP8 cache ---------------------------------------------------------
+    def _fp8_alloc(self, batch: int, cap: int, zero: bool):
+        new = torch.zeros if zero else torch.empty
+        lead = (batch, self.n_kv_heads, cap)
+        return (new(*lead, self.k_head_dim, dtype=torch.uint8,
+                    device=self.device),
+                new(*lead, self.v_head_dim, dtype=torch.uint8,
+                    device=self.device),
+                new(*lead, dtype=torch.float32, device=self.device),
+                new(*lead, dtype=torch.float32, device=self.device))
+
+    def _fp8_grow(self, batch: int, new_cap: int):
+        bufs = self._fp8_alloc(batch, new_cap, zero=False)
+        if self._k is not None and self.offset > 0:
+            for new, old in zip(bufs, (self._k, self._v, self._ks, self._vs)):
+                new[:, :, : self.offset] = old[:, :, : self.offset]
+        self._k, self._v, self._ks, self._vs = bufs
+
+    def _fp8_update(self, k: torch.Tensor, v: torch.Tensor):
+        from . import reference as ref
+        k8, ks = ref.kv_fp8_quantize(k)
+        v8, vs = ref.kv_fp8_quantize(v)
+        if self.graph_pos is not None:
+            idx = self.graph_pos.to(torch.long)
+            if idx.numel() > 1:  # per-row positions: row b lands at pos[b]
+                rows = torch.arange(idx.numel(), device=idx.device)
+                self._k[rows, :, idx] = k8[:, :, 0]
+                self._v[rows, :, idx] = v8[:, :, 0]
+                self._ks[rows, :, idx] = ks[:, :, 0]
+                self._vs[rows, :, idx] = vs[:, :, 0]
+            else:
+                self._k.index_copy_(2, idx, k8)
+                self._v.index_copy_(2, idx, v8)
+                self._ks.index_copy_(2, idx, ks)
+                self._vs.index_copy_(2, idx, vs)
+            return (ref.kv_fp8_dequantize(self._k, self._ks),
+                    ref.kv_fp8_dequantize(self._v, self._vs))
+        B, H, T, _ = k.shape
+        self._ensure(B, self.offset + T)
+        sl = slice(self.offset, self.offset + T)
+        self._k[:, :, sl], self._v[:, :, sl] = k8, v8
+        self._ks[:, :, sl], self._vs[:, :, sl] = ks, vs
+        self.offset += T
+        n = self.offset
+        return (ref.kv_fp8_dequantize(self._k[:, :, :n], self._ks[:, :, :n]),
+                ref.kv_fp8_dequantize(self._v[:, :, :n], self._vs[:, :, :n]))
+
+    def append_rope_kv_fp8(self, k: torch.Tensor, v: torch.Tensor,
+                           cos: torch.Tensor, sin: torch.Tensor):
+        """Fused FP8 append: RoPE (half-split) the new k rows [B, T, Hkv, D],
+        quantize k and v per row and scatter bytes and scales at the
+        position (host offset or graph_pos), in one launch.  GPU-only;
+        returns the full buffers (k8, ks, v8, vs)."""
+        from .. import ops as _ops
+        ext = _ops.hip_ext()
+        B, T = k.shape[0], k.shape[1]
+        if self.graph_pos is not None:
+            ext.rope_append_kv_fp8(k, v, cos, sin, self._k, self._ks,
+                                   self._v, self._vs, pos=self.graph_pos)
+        else:
+            self._ensure(B, self.offset + T)
+            ext.rope_append_kv_fp8(k, v, cos, sin, self._k, self._ks,
+                                   self._v, self._vs, pos0=self.offset)
+            self.offset += T
+        return self._k, self._ks, self._v, self._vs
+
+    def dequant_views(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """bf16 (k, v) [B, Hkv, S, D] of an FP8 cache: the first ``offset``
+        positions, or the whole capacity in graph mode."""
+        from .. import ops as _ops
+        n = self.capacity if self.graph_pos is not None else self.offset
+        if _ops.use_native(self._k):
+            ext = _ops.hip_ext()
+            return (ext.kv_fp8_dequant(self._k, self._ks, n),
+                    ext.kv_fp8_dequant(self._v, self._vs, n))
+        from . import reference as ref
+        return (ref.kv_fp8_dequantize(self._k[:, :, :n], self._ks[:, :, :n]),
+                ref.kv_fp8_dequantize(self._v[:, :, :n], self._vs[:, :, :n]))
+
     @property
     def k(self) -> Optional[torch.Tensor]:
         return None if self._k is None else self._k[:, :, : self.offset]
@@ -175,6 +268,12 @@ class KVCache:
         """Allocate exactly ``capacity`` positions and fix the size: the
         slot pool of continuous batching (one row per sequence)."""
         b = batch if batch is not None else self.batch_size
+        if self.fp8:
+            self._k, self._v, self._ks, self._vs = self._fp8_alloc(
+                b, capacity, zero=True)
+            self.batch_size = b
+            self._fixed = True
+            return
         shape = (b, self.n_kv_heads, capacity)
         self._k = torch.zeros(*shape, self.k_head_dim, dtype=self.dtype,
                               device=self.device)
@@ -193,6 +292,8 @@ class KVCache:
         c = KVCache(self.n_kv_heads, self.k_head_dim, self.v_head_dim,
                     dtype=self.dtype, device=self.device, batch_size=1)
         c._k, c._v = self._k[i:i + 1], self._v[i:i + 1]
+        if self.fp8:
+            c._ks, c._vs = self._ks[i:i + 1], self._vs[i:i + 1]
         c._fixed = True
         return c
 

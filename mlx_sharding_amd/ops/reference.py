@@ -129,6 +129,43 @@ def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# FP8 KV cache: the storage format (kv_fp8.hip implements the same)
+# ---------------------------------------------------------------------------
+
+KV_FP8_EMIN, KV_FP8_EMAX = -100, 120
+
+
+def kv_fp8_quantize(x: torch.Tensor):
+    """Quantize rows ``x`` [..., D] to OCP e4m3 bytes with one power-of-two
+    scale per row: returns (bytes uint8 [..., D], scale fp32 [...]).
+
+    scale = 2^e with e the smallest integer such that amax(row) <= 448 * 2^e,
+    clamped to [-100, 120]; an all-zero row takes e = -100.  The byte is the
+    round-to-nearest-even e4m3 code of x * 2^-e, which is exact in fp32, so
+    the whole quantization is one deterministic rounding.  e comes from
+    frexp, not a floating log2: amax = m * 2^k with m in [0.5, 1) and
+    448 = 0.875 * 2^9, hence e = k - 9, one more when m > 0.875.  NaN or Inf
+    inputs are out of contract."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    m, k = torch.frexp(amax)
+    e = k.to(torch.int32) - 9 + (m > 0.875).to(torch.int32)
+    e = torch.where(amax == 0, torch.full_like(e, KV_FP8_EMIN), e)
+    e = e.clamp(KV_FP8_EMIN, KV_FP8_EMAX)
+    one = torch.ones_like(amax)
+    codes = (xf * torch.ldexp(one, -e)[..., None]).to(torch.float8_e4m3fn)
+    return codes.view(torch.uint8), torch.ldexp(one, e)
+
+
+def kv_fp8_dequantize(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bytes [..., D] (uint8 or float8_e4m3fn) and scale [...] -> bf16.
+    scale * code is exact in bf16 (4 significant bits, power-of-two scale)."""
+    if codes.dtype != torch.float8_e4m3fn:
+        codes = codes.view(torch.float8_e4m3fn)
+    return (codes.float() * scale[..., None]).to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------------
 # Attention
 # ---------------------------------------------------------------------------
 

@@ -629,9 +629,14 @@ def main(argv=None):
                         "requests in one batched step (default "
                         "MLXS_MAX_BATCH or 1 = off; single-stage only; "
                         "MLXS_PREFIX_CACHE is ignored while batching)")
+    p.add_argument("--kv-dtype", choices=["bf16", "fp8"], default=None,
+                   help="KV cache dtype (sets MLXS_AMD_KV_DTYPE): fp8 halves "
+                        "the cache of llama-family models, head dim 64/128")
     p.add_argument("--log-level", type=str, default="INFO",
                    choices=["DEBUG", "INFO", "WARNING", "ERROR", "CRITICAL"])
     args = p.parse_args(argv)
+    if args.kv_dtype:
+        os.environ["MLXS_AMD_KV_DTYPE"] = args.kv_dtype
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO))
     if args.adapter_path:
         log.warning("--adapter-path is accepted for CLI parity but adapters "

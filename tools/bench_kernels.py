@@ -265,6 +265,53 @@ def bench_gqa_decode(ext, dev="cuda", window_s=0.25, batches=(1, 16, 64),
                           f"  diff {diff.item():.1e}", flush=True)
 
 
+def bench_gqa_decode_fp8(ops, ext, dev="cuda", window_s=0.25,
+                         batches=(1, 16, 64), lengths=(512, 4096, 16384)):
+    """Decode attention over the FP8 KV cache (gqa_decode_fp8) against the
+    bf16 path ops.attention routes the same shape to, alternated in one
+    process after warm-up, two rounds of one window each.  Shapes (Hq, Hkv,
+    D): llama-3-8b (32, 8, 128), llama-3-70b (64, 8, 128), tinyllama (32, 4,
+    64).  "host" passes the length L; "device" an int32 [B] position L - 1
+    over the whole capacity (the largest length).  TB/s is the KV bytes the
+    kernel has to read (B*Hkv*L*2*D elements of 2 or 1 bytes, plus 8 bytes of
+    scales per key for FP8) over the faster round."""
+    shapes = [(32, 8, 128), (64, 8, 128), (32, 4, 64)]
+    cap, bmax = max(lengths), max(batches)
+    print("Hq Hkv D B L mode: bf16 us (r0 r1) TB/s | fp8 us (r0 r1) TB/s | "
+          "bf16/fp8 (min..max over rounds)")
+    for Hq, Hkv, D in shapes:
+        scale = D ** -0.5
+        qb = torch.randn(bmax, Hq, 1, D, dtype=torch.bfloat16, device=dev)
+        kb = torch.randn(bmax, Hkv, cap, D, dtype=torch.bfloat16, device=dev)
+        vb = torch.randn(bmax, Hkv, cap, D, dtype=torch.bfloat16, device=dev)
+        for B in batches:
+            q = qb[:B]
+            k8, ks = ops.kv_fp8_quantize(kb[:B])
+            v8, vs = ops.kv_fp8_quantize(vb[:B])
+            for L in lengths:
+                for mode in ("host", "device"):
+                    if mode == "host":
+                        k, v, pos, n = kb[:B, :, :L], vb[:B, :, :L], None, L
+                    else:
+                        k, v, n = kb[:B], vb[:B], -1
+                        pos = torch.full((B,), L - 1, dtype=torch.int32,
+                                         device=dev)
+                    fns = (lambda: ops.attention(q, k, v, scale, pos_dev=pos),
+                           lambda: ext.gqa_decode_fp8(q, k8, ks, v8, vs, scale,
+                                                      pos, n))
+                    diff = (fns[0]().float() - fns[1]().float()).abs().max()
+                    t = [[_window_us(fn, window_s) for fn in fns]
+                         for _ in range(2)]  # alternate the two kernels
+                    old, new = (t[0][0], t[1][0]), (t[0][1], t[1][1])
+                    tb16 = B * Hkv * L * 2 * D * 2 / 1e6
+                    tb8 = B * Hkv * L * (2 * D + 8) / 1e6
+                    print(f"{Hq:2d} {Hkv} {D:3d} B={B:2d} L={L:5d} {mode:6s}: "
+                          f"{old[0]:7.1f} {old[1]:7.1f} {tb16 / min(old):5.2f} | "
+                          f"{new[0]:7.1f} {new[1]:7.1f} {tb8 / min(new):5.2f} | "
+                          f"{min(old) / max(new):5.2f}..{max(old) / min(new):5.2f}"
+                          f"  diff {diff.item():.1e}", flush=True)
+
+
 def bench_mla_chunk(ops, ext, dev="cuda", iters=200):
     """One layer's attention section for T new tokens over a cached prefix
     of a V2-Lite / V3 geometry (rows 576 / 512, nope 128, vd 128), B=1, two
@@ -710,6 +757,10 @@ def main():
     ap.add_argument("--gqa-decode", action="store_true",
                     help="only the GQA decode comparison: the scalar "
                          "attn_decode kernel vs the MFMA gqa_decode kernel")
+    ap.add_argument("--gqa-decode-fp8", action="store_true",
+                    help="only the FP8 KV cache rows: gqa_decode_fp8 vs the "
+                         "bf16 decode path of the same shape (lengths 512, "
+                         "4096 and 16384)")
     ap.add_argument("--lengths", type=int, nargs="+",
                     default=[512, 2048, 4096, 8192],
                     help="key lengths of --gqa-decode; the largest is the "
@@ -730,6 +781,9 @@ def main():
         return
     if args.gqa_decode:
         bench_gqa_decode(ext, dev, lengths=tuple(args.lengths))
+        return
+    if args.gqa_decode_fp8:
+        bench_gqa_decode_fp8(ops, ext, dev)
         return
     if args.mla_only:
         bench_mla(ops, ext, dev)
