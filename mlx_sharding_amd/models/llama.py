@@ -79,7 +79,9 @@ class LlamaAttention(nn.Module):
         quantized and appended by one kernel; T == 1 runs the FP8 flash-decode
         kernel on the bytes, T > 1 (cold or chunked prefill, prefix-cache
         tails) dequantizes the cached rows into bf16 scratch for the existing
-        prefill attention.  Prefill and decode therefore attend the SAME
+        prefill attention, unless ops.gqa_chunk_route sends a chunk over a
+        cached prefix to the chunk kernel, which also reads the bytes (and
+        stages the same dequantized values).  Prefill and decode attend the SAME
         quantized values, new rows included, so cold-vs-chunked prefill and
         prefix-cache reuse stay equal to one another as with a bf16 cache."""
         B, _, T, _ = q.shape
@@ -90,6 +92,12 @@ class LlamaAttention(nn.Module):
             out = ops.gqa_decode_fp8(q, k8, ks, v8, vs, self.scale, pos=gp,
                                      length=None if gp is not None
                                      else cache.offset)
+        elif gp is None and ops.gqa_chunk_route(
+                q.shape[1] // k8.shape[1], q.shape[3], B, k8.shape[1], T,
+                cache.offset):
+            # a chunk over a cached prefix attends the bytes directly
+            out = ops.gqa_chunk_fp8(q, k8, ks, v8, vs, self.scale,
+                                    cache.offset)
         else:
             kd, vd = cache.dequant_views()
             out = ops.attention(q, kd, vd, self.scale, causal_offset=offset,

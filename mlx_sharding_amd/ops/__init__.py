@@ -143,6 +143,14 @@ def attention(q, k, v, scale: float, causal_offset: int = 0,
                                       pos_dev)
             return ext.attn_decode(q, k, v, scale, softcap, sliding_window,
                                    pos_dev)
+        if (cache_layout and not softcap and not sliding_window
+                and pos_dev is None and v.stride(2) == v.shape[3]
+                and q.shape[3] == v.shape[3]
+                and causal_offset == k.shape[2] - q.shape[2]
+                and gqa_chunk_route(q.shape[1] // k.shape[1], q.shape[3],
+                                    q.shape[0], k.shape[1], q.shape[2],
+                                    k.shape[2])):
+            return ext.gqa_chunk(q, k, v, scale)
         if (cache_layout
                 and ext.attn_prefill_shape_ok(q.shape[3], v.shape[3])):
             return ext.attn_prefill(q, k, v, scale, softcap, sliding_window,
@@ -272,6 +280,78 @@ def gqa_decode_fp8(q, k8, ks, v8, vs, scale: float, pos=None, length=None):
     k = ref.kv_fp8_dequantize(k8[:, :, :S], ks[:, :, :S])
     v = ref.kv_fp8_dequantize(v8[:, :, :S], vs[:, :, :S])
     return attention(q, k, v, scale, causal_offset=S - 1, pos_dev=pos)
+
+
+_GQA_CHUNK_ENV = "MLXS_AMD_GQA_CHUNK"
+
+
+def gqa_chunk_route(G: int, D: int, batch: int, hkv: int, T: int, S: int,
+                    device_pos: bool = False) -> bool:
+    """True when causal attention of T > 1 new tokens (the last T of S
+    cached rows) of G = Hq/Hkv heads per KV head over separate head-dim-D
+    caches should take the MFMA chunk kernel (gqa_chunk.hip) instead of
+    attn_prefill.  A call without a cached prefix (S == T, cold prefill) and
+    a call under a device position are never routed, whatever the setting.
+    MLXS_AMD_GQA_CHUNK=0 never routes; =1 routes every call the kernel has
+    an instantiation for.  Unset, only the regions where the kernel beat
+    the attn_prefill path in every measured row by more than the run-to-run
+    spread are routed (PERFORMANCE.md, "GQA chunk attention")."""
+    env = os.environ.get(_GQA_CHUNK_ENV)
+    if env not in (None, "0", "1"):
+        raise ValueError(f"{_GQA_CHUNK_ENV} must be 0 or 1, got {env!r}")
+    ext = hip_ext()
+    if (env == "0" or device_pos or T < 1 or S <= T or ext is None
+            or not ext.gqa_chunk_shape_ok(G, D, D)):
+        return False
+    if env == "1":
+        return True
+    return _gqa_chunk_measured(G, D, batch, hkv, T, S - T)
+
+
+def _gqa_chunk_measured(G: int, D: int, batch: int, hkv: int, T: int,
+                        prefix: int) -> bool:
+    """The default regions of gqa_chunk_route: head dim 128 at G = 4, 7 and
+    8 (llama-3-8b, qwen2-7b, llama-3-70b) and head dim 64 at G = 8
+    (tinyllama), chunks of 4 to 64 tokens over a prefix >= 512 at batch 1
+    to 8.  The kernel won every one of those rows, bf16 and FP8 cache, by
+    1.7x (batch 8, T = 64, head dim 64) to 33x (batch 1, T = 4, prefix
+    32768) against a spread of at most 1.1%.  The prefix bound is a lower
+    bound (the margin grows with the prefix); the margin shrinks as T and
+    the batch grow, so those stay inside what the table holds, and
+    everything not measured stays on attn_prefill."""
+    if not (4 <= T <= 64 and 1 <= batch <= 8 and prefix >= 512):
+        return False
+    return (D == 128 and G in (4, 7, 8)) or (D == 64 and G == 8)
+
+
+def gqa_chunk(q, k, v, scale: float):
+    """Causal grouped-query attention of T >= 1 new tokens over a cached
+    prefix on the MFMA chunk kernel.
+
+    q [B, Hq, T, D] with any batch/head/token strides (the transposed view
+    apply_rope returns is read in place); k/v are cache views [B, Hkv, S, D]
+    over separate capacity buffers whose last T rows are the new tokens;
+    D is 64 or 128 and 1 <= Hq/Hkv <= 16.  Token t attends keys
+    [0, S - T + t].  Returns [B, Hq, T, D] (a view of [B, T, Hq, D])."""
+    if _use_hip(q):
+        return _require_ext("gqa_chunk").gqa_chunk(q, k, v, scale)
+    return ref.attention(q, k, v, scale,
+                         causal_offset=k.shape[2] - q.shape[2])
+
+
+def gqa_chunk_fp8(q, k8, ks, v8, vs, scale: float, length: int):
+    """gqa_chunk over an FP8 KV cache: k8 / v8 are the byte buffers
+    [B, Hkv, Scap, D] with their fp32 scales ks / vs [B, Hkv, Scap], and the
+    new tokens are the last T of the first ``length`` rows.  The kernel
+    widens the bytes while it stages them; its output equals gqa_chunk on
+    the dequantized rows bit for bit.  Returns [B, Hq, T, D]."""
+    S = int(length)
+    if _use_hip(q):
+        return _require_ext("gqa_chunk_fp8").gqa_chunk_fp8(q, k8, ks, v8, vs,
+                                                           scale, S)
+    k = ref.kv_fp8_dequantize(k8[:, :, :S], ks[:, :, :S])
+    v = ref.kv_fp8_dequantize(v8[:, :, :S], vs[:, :, :S])
+    return ref.attention(q, k, v, scale, causal_offset=S - q.shape[2])
 
 
 def mla_decode_enabled() -> bool:

@@ -63,6 +63,13 @@ void launch_mla_chunk(const void*, const void*, const void*, void*, float*,
                       long, long, long, long, long, long, hipStream_t);
 bool mla_chunk_supported_shape(int, int, int);
 int mla_chunk_nsplit(int, long, long);
+void launch_gqa_chunk(const void*, const void*, const void*, const float*,
+                      const float*, void*, float*, float*, int, int, int, int,
+                      int, int, long, int, float, long, long, long,
+                      hipStream_t);
+bool gqa_chunk_supported_shape(int, int, int);
+int gqa_chunk_nsplit(long, long);
+long gqa_chunk_blocks(int, int, int, int);
 void launch_attn_prefill(const void*, const void*, const void*, void*, int,
                          int, int, int, int, long, long, int, int, float,
                          float, int, int, hipStream_t);
@@ -924,6 +931,97 @@ torch::Tensor mla_chunk(torch::Tensor q_nope, torch::Tensor q_rope,
                    q_nope.stride(2), q_rope.stride(0), q_rope.stride(1),
                    q_rope.stride(2), cur_stream());
   return out;
+}
+
+// MFMA chunk attention for grouped-query models (gqa_chunk.hip): T >= 1 new
+// tokens, already appended as the last T of the S cached rows, attend keys
+// [0, S - T + t].  q [B, Hq, T, D] is read in place through its (batch,
+// head, token) strides.  Shared tail of the two entry points below: k / v are
+// the bases of [B, Hkv, Scap, D] buffers (bf16, or bytes with scales).
+// Returns the [B, Hq, T, D] view of the kernel's [B, T, Hq, D] output.
+torch::Tensor gqa_chunk_impl(const torch::Tensor& q, const void* k,
+                             const void* v, const float* ks, const float* vs,
+                             int Hkv, int S, long Scap, int Dk, int Dv,
+                             double scale, const char* name) {
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 4, name, ": q must be [B, Hq, T, D]");
+  const int B = q.size(0), Hq = q.size(1), T = q.size(2), D = q.size(3);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, name,
+              ": Hq must be divisible by Hkv");
+  const int G = Hq / Hkv;
+  TORCH_CHECK(G <= 16, name, " serves 1 to 16 heads per KV head, got ", G);
+  TORCH_CHECK(D == Dk && gqa_chunk_supported_shape(G, Dk, Dv), name,
+              ": unsupported shape G=", G, " Dk=", Dk, " Dv=", Dv,
+              " (q rows of ", D, ")");
+  TORCH_CHECK(T >= 1 && T <= S, name, ": T=", T,
+              " new tokens must be among the S=", S, " cached rows");
+  TORCH_CHECK(S <= Scap, name, ": length outside the capacity");
+  // the kernel reads q with 16-byte loads
+  TORCH_CHECK(q.stride(3) == 1 && q.stride(0) % 8 == 0 &&
+                  q.stride(1) % 8 == 0 && q.stride(2) % 8 == 0 &&
+                  (reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0,
+              name, ": q rows must be contiguous and 16-byte aligned");
+  const int nsplit = gqa_chunk_nsplit(gqa_chunk_blocks(B, Hkv, T, G), (long)S);
+  auto out = torch::empty({B, T, Hq, D}, q.options());
+  float* part_o = nullptr;
+  float* part_ml = nullptr;
+  torch::Tensor po, pml;
+  if (nsplit > 1) {
+    auto fopts = q.options().dtype(torch::kFloat32);
+    po = torch::empty({(long)B * T * Hq * nsplit * D}, fopts);
+    pml = torch::empty({(long)B * T * Hq * nsplit * 2}, fopts);
+    part_o = po.data_ptr<float>();
+    part_ml = pml.data_ptr<float>();
+  }
+  launch_gqa_chunk(q.data_ptr(), k, v, ks, vs, out.data_ptr(), part_o, part_ml,
+                   nsplit, B, T, Hq, Hkv, S, Scap, D, (float)scale,
+                   q.stride(0), q.stride(1), q.stride(2), cur_stream());
+  return out.transpose(1, 2);
+}
+
+// k/v: cache views [B, Hkv, S, D] over separate [B, Hkv, Scap, D] buffers.
+torch::Tensor gqa_chunk(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                        double scale) {
+  check_bf16(k, "k");
+  check_bf16(v, "v");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+              "gqa_chunk: q must be [B, Hq, T, D], k/v [B, Hkv, S, D]");
+  const int B = q.size(0), Hkv = k.size(1), S = k.size(2);
+  const int Dk = k.size(3), Dv = v.size(3);
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && v.size(1) == Hkv &&
+                  v.size(2) == S, "k/v must match q's batch and each other");
+  TORCH_CHECK(k.stride(3) == 1 && v.stride(3) == 1 && k.stride(2) == Dk &&
+                  v.stride(2) == Dv &&
+                  (reinterpret_cast<uintptr_t>(k.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(v.data_ptr()) & 15) == 0,
+              "gqa_chunk: K/V rows must be contiguous and 16-byte aligned");
+  TORCH_CHECK(k.stride(1) % Dk == 0 && v.stride(1) % Dv == 0 &&
+                  k.stride(1) / Dk == v.stride(1) / Dv &&
+                  k.stride(1) / Dk >= S &&
+                  (B == 1 || (k.stride(0) == Hkv * k.stride(1) &&
+                              v.stride(0) == Hkv * v.stride(1))),
+              "gqa_chunk: K/V head and batch strides must be a whole number "
+              "of rows of one capacity");
+  return gqa_chunk_impl(q, k.data_ptr(), v.data_ptr(), nullptr, nullptr, Hkv,
+                        S, k.stride(1) / Dk, Dk, Dv, scale, "gqa_chunk");
+}
+
+// k8 / v8: the full byte buffers with their scales; rows attend the first
+// `length` keys, the new tokens being the last T of them.
+torch::Tensor gqa_chunk_fp8(torch::Tensor q, torch::Tensor k8,
+                            torch::Tensor ks, torch::Tensor v8,
+                            torch::Tensor vs, double scale, int64_t length) {
+  check_kv8_buffer(k8, ks, "K");
+  check_kv8_buffer(v8, vs, "V");
+  TORCH_CHECK(q.dim() == 4 && k8.sizes() == v8.sizes() &&
+                  k8.size(0) == q.size(0),
+              "k8/v8 must match q's batch and each other");
+  TORCH_CHECK(length >= 0 && length <= k8.size(2),
+              "gqa_chunk_fp8: length outside the capacity");
+  return gqa_chunk_impl(q, k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(),
+                        vs.data_ptr<float>(), (int)k8.size(1), (int)length,
+                        k8.size(2), (int)k8.size(3), (int)v8.size(3), scale,
+                        "gqa_chunk_fp8");
 }
 
 // q [B, Hq, T, Dk]; k/v cache views [B, Hkv, S, D] (row-contiguous)
@@ -1932,6 +2030,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("mla_chunk_nsplit", [](int64_t B, int64_t rows, int64_t span) {
     return mla_chunk_nsplit((int)B, (long)rows, (long)span);
+  });
+  m.def("gqa_chunk", &gqa_chunk, pybind11::arg("q"), pybind11::arg("k"),
+        pybind11::arg("v"), pybind11::arg("scale"));
+  m.def("gqa_chunk_fp8", &gqa_chunk_fp8, pybind11::arg("q"),
+        pybind11::arg("k8"), pybind11::arg("ks"), pybind11::arg("v8"),
+        pybind11::arg("vs"), pybind11::arg("scale"), pybind11::arg("length"));
+  m.def("gqa_chunk_shape_ok", [](int64_t g, int64_t dk, int64_t dv) {
+    return gqa_chunk_supported_shape((int)g, (int)dk, (int)dv);
+  });
+  m.def("gqa_chunk_nsplit", [](int64_t blocks, int64_t span) {
+    return gqa_chunk_nsplit((long)blocks, (long)span);
   });
   m.def("attn_prefill", &attn_prefill);
   m.def("attn_prefill_shape_ok", [](int64_t dk, int64_t dv) {

@@ -312,6 +312,67 @@ def bench_gqa_decode_fp8(ops, ext, dev="cuda", window_s=0.25,
                           f"  diff {diff.item():.1e}", flush=True)
 
 
+def bench_gqa_chunk(ops, ext, dev="cuda", window_s=0.12, rounds=3,
+                    chunks=(4, 16, 64), prefixes=(512, 4096, 32768),
+                    batches=(1, 8)):
+    """T new tokens over a cached prefix: gqa_chunk / gqa_chunk_fp8 against
+    what the same call runs without them (attn_prefill on the bf16 cache;
+    kv_fp8_dequant of K and V + attn_prefill on the FP8 cache), the four
+    paths alternated in one process on the same tensors after warm-up,
+    `rounds` rounds of one window each.  Shapes (Hq, Hkv, D): llama-3-8b
+    (32, 8, 128), llama-3-70b (64, 8, 128), qwen2-7b (28, 4, 128), tinyllama
+    (32, 4, 64).  Per path: median us and (max - min) / median over the
+    rounds; old/new is min(old) / max(new) .. max(old) / min(new)."""
+    shapes = [(32, 8, 128), (64, 8, 128), (28, 4, 128), (32, 4, 64)]
+    cap, bmax, tmax = max(prefixes) + max(chunks), max(batches), max(chunks)
+    print("Hq Hkv D B T prefix: prefill us spread | chunk us spread old/new "
+          "|| dequant+prefill us spread | chunk_fp8 us spread old/new",
+          flush=True)
+    worst = 0.0
+    for Hq, Hkv, D in shapes:
+        scale = D ** -0.5
+        qb = torch.randn(bmax, tmax, Hq, D, dtype=torch.bfloat16, device=dev)
+        kb = torch.randn(bmax, Hkv, cap, D, dtype=torch.bfloat16, device=dev)
+        vb = torch.randn(bmax, Hkv, cap, D, dtype=torch.bfloat16, device=dev)
+        k8b, ksb = ops.kv_fp8_quantize(kb)
+        v8b, vsb = ops.kv_fp8_quantize(vb)
+        for B in batches:
+            k8, ks, v8, vs = (t[:B].contiguous() for t in (k8b, ksb, v8b, vsb))
+            for T in chunks:
+                q = qb[:B, :T].transpose(1, 2)
+                for P in prefixes:
+                    S = P + T
+                    k, v = kb[:B, :, :S], vb[:B, :, :S]
+
+                    def old8():
+                        return ext.attn_prefill(
+                            q, ext.kv_fp8_dequant(k8, ks, S),
+                            ext.kv_fp8_dequant(v8, vs, S), scale, 0.0, 0, P)
+
+                    fns = (lambda: ext.attn_prefill(q, k, v, scale, 0.0, 0, P),
+                           lambda: ext.gqa_chunk(q, k, v, scale), old8,
+                           lambda: ext.gqa_chunk_fp8(q, k8, ks, v8, vs, scale,
+                                                     S))
+                    d16 = (fns[0]().float() - fns[1]().float()).abs().max()
+                    d8 = (fns[2]().float() - fns[3]().float()).abs().max()
+                    t = [[_window_us(fn, window_s) for fn in fns]
+                         for _ in range(rounds)]  # alternate the paths
+                    cols = [sorted(r[i] for r in t) for i in range(4)]
+                    med = [c[len(c) // 2] for c in cols]
+                    spr = [(c[-1] - c[0]) / m for c, m in zip(cols, med)]
+                    worst = max(worst, *spr)
+                    line = f"{Hq:2d} {Hkv} {D:3d} B={B} T={T:2d} P={P:5d}:"
+                    for o, n in ((0, 1), (2, 3)):
+                        line += (f" {med[o]:8.1f} {100 * spr[o]:4.1f}% |"
+                                 f" {med[n]:8.1f} {100 * spr[n]:4.1f}%"
+                                 f" {cols[o][0] / cols[n][-1]:5.2f}.."
+                                 f"{cols[o][-1] / cols[n][0]:5.2f} |")
+                    print(line + f" diff {d16.item():.1e} {d8.item():.1e}",
+                          flush=True)
+    print(f"largest (max - min) / median over the rounds: {100 * worst:.1f}%",
+          flush=True)
+
+
 def bench_mla_chunk(ops, ext, dev="cuda", iters=200):
     """One layer's attention section for T new tokens over a cached prefix
     of a V2-Lite / V3 geometry (rows 576 / 512, nope 128, vd 128), B=1, two
@@ -754,6 +815,10 @@ def main():
     ap.add_argument("--mla-chunk", action="store_true",
                     help="only the short-chunk-over-a-prefix comparison: "
                          "expanded prefill vs the absorbed mla_chunk path")
+    ap.add_argument("--gqa-chunk", action="store_true",
+                    help="only the chunk-over-a-prefix comparison for the "
+                         "GQA models: attn_prefill (after kv_fp8_dequant for "
+                         "the FP8 cache) vs gqa_chunk / gqa_chunk_fp8")
     ap.add_argument("--gqa-decode", action="store_true",
                     help="only the GQA decode comparison: the scalar "
                          "attn_decode kernel vs the MFMA gqa_decode kernel")
@@ -778,6 +843,9 @@ def main():
 
     if args.moe_route:
         bench_moe_route(ops, ref, dev)
+        return
+    if args.gqa_chunk:
+        bench_gqa_chunk(ops, ext, dev)
         return
     if args.gqa_decode:
         bench_gqa_decode(ext, dev, lengths=tuple(args.lengths))
